@@ -11,6 +11,15 @@ Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
 One rank per GPU; ring hops are RCCL send/recv over xGMI. A "step" = every
 sequence in every microbatch advances one token (one full ring round).
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: one prefill (to fill
+the KV cache), warmup, the timed steps. ``--full`` adds the p50 TTFT over
+several prefills and the individually timed step samples. ``--dump-outputs
+DIR`` writes what the last timed step computed as DIR/<name>.npy; weights
+and prompt tokens are seeded, so the inputs are identical from run to run.
+On the GPU the benchmark switches the decode GEMMs to their reproducible
+split-k mode (dnet_amd.ops.set_reproducible), so the dense-model outputs
+are identical from run to run as well.
 """
 from __future__ import annotations
 
@@ -47,6 +56,43 @@ from dnet_amd.parallel.comm import init_from_env
 from dnet_amd.parallel.ring import RingExecutor
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # all dumped arrays together stay under 64 MB
+
+
+def _dump_outputs(out_dir: str, ex: RingExecutor) -> None:
+    """Write what the last decode step produced as <out_dir>/<name>.npy:
+
+    tokens  float64 [mb_count, mb_size]         sampled token ids (first stage)
+    logits  float32 [mb_count, mb_size, cols]   lm_head output (last stage)
+    logits_columns  float64 [cols]              vocab ids of the logit columns
+
+    All vocab columns are kept when they fit the budget; otherwise a fixed,
+    seeded sample of columns (the same ones in every run)."""
+    import numpy as np
+    # one writer per file: tp_rank is the rank inside the stage group for
+    # tensor AND context parallelism (tp and cp are mutually exclusive), so
+    # only the group's rank 0 of the first / last stage writes
+    if ex.tp_rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    if ex.is_first:
+        toks = torch.stack([t.cpu() for t in ex.tokbuf]).to(torch.float64)
+        np.save(os.path.join(out_dir, "tokens.npy"), toks.numpy())
+    if ex.is_last:
+        V = ex.cfg.vocab_size
+        rows = ex.mb_count * ex.mb_size
+        keep = min(V, max(1, DUMP_BUDGET_BYTES // (4 * rows) - 2))
+        if keep < V:
+            g = torch.Generator().manual_seed(2024)
+            cols = torch.randperm(V, generator=g)[:keep].sort().values
+        else:
+            cols = torch.arange(V)
+        logits = torch.stack([l.float().cpu()[:, cols] for l in ex.logits_buf])
+        np.save(os.path.join(out_dir, "logits.npy"), logits.numpy())
+        np.save(os.path.join(out_dir, "logits_columns.npy"),
+                cols.to(torch.float64).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -76,10 +122,23 @@ def main():
     ap.add_argument("--residency", type=int, default=0,
                     help="GPU-resident layers per rank (0=all; <local layers "
                          "enables host-DRAM weight streaming)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure p50 TTFT over several prefills and "
+                         "individually timed step samples (extra GPU time)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs (tokens, logits) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank, world, device = init_from_env()
     on_gpu = device.type == "cuda"
+    if on_gpu:
+        # order-independent split-k sums: without it the last bit of every
+        # decode GEMM varies per run and greedy sampling turns that into
+        # different tokens, so two runs (or two builds) could not be
+        # compared output for output. Same kernels, same speed.
+        import dnet_amd.ops as ops
+        ops.set_reproducible(True)
 
     quant = None
     if args.quant == "int8":
@@ -113,10 +172,12 @@ def main():
         if on_gpu:
             torch.cuda.synchronize()
 
-    # TTFT: p50 over >= 5 prefills (a single measurement is
-    # not a p50); each prefill resets the ring KV first
+    # TTFT (--full): p50 over >= 5 prefills (a single
+    # measurement is not a p50); each prefill resets the ring KV first.
+    # A plain run prefills once, untimed, only to fill the KV cache.
     ttft_samples = []
-    n_prefills = max(1, int(os.environ.get("DNET_BENCH_PREFILLS", "5")))
+    n_prefills = (max(1, int(os.environ.get("DNET_BENCH_PREFILLS", "5")))
+                  if args.full else 1)
     for i in range(n_prefills):
         ex.reset()
         barrier_sync()
@@ -136,11 +197,16 @@ def main():
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
-    # self-corroboration: a few individually timed steps AFTER the timed
-    # region (sync per step), so the record shows per-step times without
-    # cross-referencing profiles/
+    # what the last timed step computed, copied out before anything else
+    # advances the ring
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, ex)
+
+    # self-corroboration (--full): a few individually timed steps AFTER the
+    # timed region (sync per step), so the record shows per-step times
+    # without cross-referencing profiles/
     step_samples = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         barrier_sync()
         t1 = time.perf_counter()
         ex.decode_rounds(1, collect=False)
@@ -176,9 +242,6 @@ def main():
                        if quant.fmt == "mxfp4" else
                        f"int{quant.bits}-g{quant.group} weights (bf16 compute)")),
             "data": "synthetic (random tokens, random-init weights)",
-            "ttft_ms": round(ttft_ms, 1),
-            "ttft_samples_ms": [round(t, 1) for t in ttft_samples],
-            "step_samples_ms": step_samples,
             "config": {
                 "model": args.model,
                 "global_batch": total_seqs,
@@ -194,6 +257,10 @@ def main():
                 "layers": cfg.num_layers,
             },
         }
+        if args.full:
+            result["ttft_ms"] = round(ttft_ms, 1)
+            result["ttft_samples_ms"] = [round(t, 1) for t in ttft_samples]
+            result["step_samples_ms"] = step_samples
         print(json.dumps(result))
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -822,11 +822,16 @@ class RingModel:
         if self._dq_stream is None:
             self._dq_stream = torch.cuda.Stream()
         ev = torch.cuda.Event()
+        # the CONSUMER stream: wd is allocated on the side stream but read
+        # by the caller's GEMM — without recording that stream the
+        # allocator hands the block to the next prefetch while the GEMM
+        # still reads it (prefill results differed run to run)
+        consumer = torch.cuda.current_stream()
         with torch.cuda.stream(self._dq_stream):
             for lin in (nxt.qkv, nxt.o, nxt.gateup, nxt.down):
                 if lin is not None and lin.is_quant:
                     wd = lin.dequant()
-                    wd.record_stream(torch.cuda.current_stream())
+                    wd.record_stream(consumer)
                     lin._wd = wd
             ev.record(self._dq_stream)
         return ev

@@ -47,6 +47,22 @@ def _native():
     return c
 
 
+def set_reproducible(on: bool) -> None:
+    """Opt-in bit-reproducible decode GEMMs (OFF by default).
+
+    The split-k decode GEMM combines its partials with f32 atomics whose
+    arrival order varies, so results differ in the last bit from run to
+    run. When on, partials are rounded to a 2^-16 grid first, which makes
+    the additions exact (order-independent) while sums stay below 2^8 — at
+    the price of an absolute precision floor of 2^-17 per partial. Meant
+    for synthetic benchmark runs with O(1) activations whose outputs are
+    compared across runs or builds; leave it off for real checkpoints.
+    Process-wide; set it before decode graphs are captured. The MoE expert
+    kernels are not covered. CPU tensors use the reference path, which is
+    reproducible already."""
+    _native().set_splitk_exact(bool(on))
+
+
 def rmsnorm(x: torch.Tensor, residual: torch.Tensor | None, w: torch.Tensor,
             eps: float = 1e-6) -> torch.Tensor:
     if x.is_cuda:

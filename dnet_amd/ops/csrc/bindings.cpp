@@ -45,6 +45,7 @@ void dequant_int8(torch::Tensor w, torch::Tensor scales, torch::Tensor out,
 void dequant_int4(torch::Tensor w, torch::Tensor scales, torch::Tensor out,
                   int64_t group);
 void dequant_mxfp4(torch::Tensor w, torch::Tensor scales, torch::Tensor out);
+void set_splitk_exact(bool on);
 bool gemm_m16_will_defer(int64_t M, int64_t N, int64_t K, int64_t group,
                          int64_t bits, int64_t scratch_elems);
 bool gemm_m16(torch::Tensor x, torch::Tensor w,
@@ -91,6 +92,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sin_table"), py::arg("kscale"), py::arg("vscale"),
         py::arg("wpos") = c10::nullopt);
   m.def("swiglu", &dnet::swiglu, "fused SwiGLU");
+  m.def("set_splitk_exact", &dnet::set_splitk_exact,
+        "order-independent (grid-rounded) split-k partial sums on/off");
   m.def("gemm_m16_will_defer", &dnet::gemm_m16_will_defer,
         "would gemm_m16(defer_combine=true) defer for this shape");
   m.def("rope_append_f32", &dnet::rope_append_f32,

@@ -43,6 +43,22 @@ __device__ __forceinline__ bf16x8 deq4(const uint8_t* qb, const float s) {
   return b;
 }
 
+// Opt-in reproducible split-k (set_splitk_exact, OFF by default; the
+// default path adds the raw f32 partials). When on, every partial is
+// rounded to a fixed 2^-16 grid before the f32 atomic. Sums of grid values
+// stay exactly representable in f32 while their magnitude is below 2^8, so
+// the additions are exact and the total does not depend on the order in
+// which the splits arrive (plain f32 atomics at sk >= 4 give a different
+// last bit per run, and 64 layers + greedy sampling turn that into
+// different tokens). The price is an absolute precision floor: each
+// partial carries up to 2^-17 of rounding error and one below 2^-17 is
+// flushed to zero, so the mode is meant for O(1) activations (synthetic
+// benchmark runs), not for general use. Sums beyond 2^8 are still correct
+// but no longer order-independent; magnitudes from 2^7 up pass unchanged.
+__device__ __forceinline__ float splitk_grid(const float v) {
+  return rintf(v * 65536.0f) * (1.0f / 65536.0f);
+}
+
 // QBITS: 16 = bf16 weights, 8 = packed int8 (pack_int8_mfma chunk-pair
 // layout), 4 = packed int4 (pack_int4_mfma chunk-quad layout).
 // MT: number of stacked 16-row A tiles (M <= 16*MT).
@@ -54,7 +70,8 @@ __global__ void gemm_m16_kernel(const short* __restrict__ x,
                                 short* __restrict__ out,        // SPLITK==1
                                 float* __restrict__ out_f32,    // SPLITK>1
                                 const int M, const int K, const int N,
-                                const int G, const int splitk) {
+                                const int G, const int splitk,
+                                const int exact) {
   constexpr int XT = 1024 / MT;        // k per x tile (LDS ~33 KB, 4 blocks/CU)
   constexpr int SE = XT + 8;           // row stride in bf16 elems (16B pad)
   __shared__ short x_lds[16 * MT * SE];
@@ -220,7 +237,8 @@ __global__ void gemm_m16_kernel(const short* __restrict__ x,
       const int m = t * 16 + (lane >> 4) * 4 + r;
       if (m >= M) continue;
       if (splitk > 1) {
-        atomicAdd(out_f32 + (int64_t)m * N + n, a2[r]);
+        atomicAdd(out_f32 + (int64_t)m * N + n,
+                  exact ? splitk_grid(a2[r]) : a2[r]);
       } else {
         float v = a2[r];
         if (bias != nullptr) v += bits2f(bias[n]);
@@ -490,7 +508,8 @@ __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
     const short* __restrict__ x, const void* __restrict__ w,
     const short* __restrict__ scales, const short* __restrict__ bias,
     short* __restrict__ out, float* __restrict__ out_f32, const int M,
-    const int K, const int N, const int G, const int splitk) {
+    const int K, const int N, const int G, const int splitk,
+    const int exact) {
   constexpr int XT = 256;
   __shared__ short x_lds[16 * MT * XT];  // unpadded (glds image, swizzled)
   const int wave = threadIdx.x / kWave;
@@ -624,7 +643,8 @@ __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
       const int m = t * 16 + (lane >> 4) * 4 + r;
       if (m >= M) continue;
       if (splitk > 1) {
-        atomicAdd(out_f32 + (int64_t)m * N + n, a2[r]);
+        atomicAdd(out_f32 + (int64_t)m * N + n,
+                  exact ? splitk_grid(a2[r]) : a2[r]);
       } else {
         float v = a2[r];
         if (bias != nullptr) v += bits2f(bias[n]);
@@ -652,6 +672,11 @@ __global__ void f32_to_bf16_bias_kernel(const float* __restrict__ in,
 // combine would clear the flag while stale partials remain beyond its
 // own M*N region and corrupt the next bigger user.
 static int64_t g_scratch_dirty_elems = 0;
+
+// reproducible split-k (see splitk_grid); process-wide, read at launch —
+// set it before graphs are captured
+static bool g_splitk_exact = false;
+void set_splitk_exact(bool on) { g_splitk_exact = on; }
 
 static int pick_splitk(int64_t N, int64_t K, int64_t M, int64_t scratch_elems,
                        int min_pairs, int g_align) {
@@ -702,6 +727,7 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
                              bits < 16 ? std::max<int>((int)group, 64) : 64);
   const short* bptr = bias.has_value() ? (const short*)bias->data_ptr() : nullptr;
   const dim3 grid((unsigned)((N + 63) / 64), sk);
+  const int exact = g_splitk_exact ? 1 : 0;
   const short* xp = (const short*)x.data_ptr() + m0 * K;
   short* op = (short*)out.data_ptr() + m0 * N;
   float* fp = nullptr;
@@ -729,7 +755,7 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
 #define LAUNCH(QQ, TT)                                                      \
   hipLaunchKernelGGL((gemm_m16_kernel<QQ, TT>), grid, dim3(256), 0, stream, \
                      xp, w.data_ptr(), sp, bp1, op, fp, M, (int)K, (int)N,  \
-                     group, sk)
+                     group, sk, exact)
   static const bool mt4occ3 = []() {
     const char* e = getenv("DNET_GEMM_MT4OCC");
     return e == nullptr || e[0] == '3';  // default: spill-free 3-wave MT4
@@ -740,11 +766,11 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
     if (noglds)                                                             \
       hipLaunchKernelGGL((gemm_m16_stream_kernel<QQ, TT, NSC, MW, false>), \
                          grid, dim3(256), 0, stream, xp, w.data_ptr(), sp,  \
-                         bp1, op, fp, M, (int)K, (int)N, group, sk);        \
+                         bp1, op, fp, M, (int)K, (int)N, group, sk, exact); \
     else                                                                    \
       hipLaunchKernelGGL((gemm_m16_stream_kernel<QQ, TT, NSC, MW, true>),   \
                          grid, dim3(256), 0, stream, xp, w.data_ptr(), sp,  \
-                         bp1, op, fp, M, (int)K, (int)N, group, sk);        \
+                         bp1, op, fp, M, (int)K, (int)N, group, sk, exact); \
   } while (0)
 #define LAUNCH_STREAM_G8(TT)                                            \
   do {                                                                    \

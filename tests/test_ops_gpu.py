@@ -813,3 +813,86 @@ def test_deferred_combine_consumers_match_plain():
     # all consumers must have re-zeroed what they read
     scr = _get_scratch(dev)
     assert int((scr != 0).sum()) == 0, "scratch not re-zeroed by consumers"
+
+
+@pytest.fixture
+def reproducible_mode():
+    ops.set_reproducible(True)
+    try:
+        yield
+    finally:
+        ops.set_reproducible(False)
+
+
+def _splitk_case(n, k, scale=1.0):
+    from dnet_amd.ops import _get_scratch, _will_defer
+    torch.manual_seed(n + k)
+    dev = _dev()
+    x = torch.randn(64, k, dtype=torch.bfloat16, device=dev) * scale
+    wf = torch.randn(n, k, dtype=torch.bfloat16, device=dev) / 30
+    q, sc = ops.quantize_int8(wf, 128)
+    assert _will_defer(64, n, k, 128, 8, _get_scratch(dev).numel()), \
+        "shape no longer splits k; pick one that does"
+    # fp32 GEMM over the same bf16-rounded dequantized weights, on the GPU
+    out_ref = ref.gemv_int8(x, q, sc, 128).float()
+    return x, ops.pack_int8_mfma(q), sc, out_ref
+
+
+@pytest.mark.parametrize("n,k", [(5120, 5120), (7168, 5120), (5120, 27648)])
+def test_gemm_splitk_reproducible_mode(n, k, reproducible_mode):
+    """Opt-in reproducible split-k at the flagship's o / qkv / down shapes
+    (batch 64, deep splits): the same bits on every launch, and still the
+    same GEMM on all 64 rows. Kernel and reference both round the same
+    f32 sum (up to summation order and the 2^-17 grid) to bf16, so they
+    differ by at most one bf16 ulp: rtol 2^-7 (an ulp at the bottom of a
+    binade), atol 2^-10 for outputs near zero. The mean error bounds a
+    systematic bias: ~5% of 327k elements are off by one ulp (~0.03), a
+    standard error of ~1e-5; 1e-4 is below what truncating instead of
+    rounding to the grid would give at sk=16 (16 * 2^-17 = 1.2e-4)."""
+    x, qp, sc, out_ref = _splitk_case(n, k)
+    outs = [ops.gemv_int8(x, qp, sc, 128, None, packed=True) for _ in range(4)]
+    for o in outs[1:]:
+        assert torch.equal(outs[0], o)
+    err = outs[0].float() - out_ref
+    print("max|err|", err.abs().max().item(), "mean err", err.mean().item())
+    assert torch.allclose(outs[0].float(), out_ref, atol=2 ** -10,
+                          rtol=2 ** -7)
+    assert abs(err.mean().item()) < 1e-4
+
+
+def test_gemm_splitk_default_keeps_small_magnitudes():
+    """The reproducible mode is OFF unless asked for, and the default
+    split-k path has no absolute precision floor: outputs of magnitude
+    ~5e-4 (below the 2^-16 grid's useful range) keep bf16 relative
+    accuracy."""
+    x, qp, sc, out_ref = _splitk_case(5120, 27648, scale=1e-4)
+    out = ops.gemv_int8(x, qp, sc, 128, None, packed=True).float()
+    assert out_ref.abs().max() < 1e-2
+    assert torch.allclose(out, out_ref, atol=2 ** -10 * 1e-4, rtol=2 ** -7)
+
+
+def test_ring_prefill_decode_reproducible_gpu(reproducible_mode):
+    """Same seeded weights and prompt twice through prefill + decode (the
+    benchmark's path: graphs on, batch 64, int8, reproducible split-k)
+    must produce the same tokens and bit-identical logits. Prefill alone
+    (first tokens) covers the dequant prefetch: its blocks must not be
+    reused while the consumer GEMM still reads them."""
+    from dnet_amd.models import ModelConfig, PRESETS, QuantConfig
+    from dnet_amd.parallel.ring import RingExecutor
+    hf = dict(PRESETS["qwen-2.5-32b"])
+    hf["num_hidden_layers"] = 8
+    cfg = ModelConfig.from_hf(hf, quant=QuantConfig(8, 128))
+    ex = RingExecutor(cfg, 0, 1, "cuda:0", mb_count=1, mb_size=64, smax=256,
+                      seed=3, use_graphs=True)
+    g = torch.Generator().manual_seed(5)
+    tokens = torch.randint(0, cfg.vocab_size, (1, 64, 128),
+                           generator=g).to("cuda:0")
+    runs = []
+    for _ in range(2):
+        ex.reset()
+        first = ex.prefill(tokens).clone()
+        gen = ex.decode_rounds(4)
+        torch.cuda.synchronize()
+        runs.append((first, gen.clone(), ex.logits_buf[0].clone()))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)

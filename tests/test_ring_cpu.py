@@ -275,6 +275,63 @@ def test_bench_contract_multiproc_cpu(tmp_path):
     assert j["config"]["global_batch"] == 2 * 2 * 2  # mb_count(2*2) * mb_size
 
 
+def _bench_cpu(extra):
+    """One single-process bench.py run of the tiny model on the CPU path
+    (devices hidden from the child so it behaves the same on a GPU box)."""
+    import json
+    import subprocess
+    import sys
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+         "--warmup", "1", "--model", "tiny", "--quant", "bf16",
+         "--mb-size", "2", "--prompt-len", "8", "--smax", "32"] + extra,
+        capture_output=True, text=True, timeout=300, env=env,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_full_and_dump_outputs_cpu(tmp_path):
+    """A plain run carries the headline fields only; --full adds the TTFT
+    and per-step samples; --dump-outputs writes the last timed step's
+    tokens and logits, identical from run to run for the same arguments."""
+    import numpy as np
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    plain = _bench_cpu(["--dump-outputs", str(a)])
+    full = _bench_cpu(["--full", "--dump-outputs", str(b)])
+    for j in (plain, full):
+        assert j["steps"] == 3 and j["warmup"] == 1
+        assert j["value"] > 0 and j["ms_per_step"] > 0
+        assert j["unit"] == "tokens/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "bf16" and "metric" in j
+        # value is derived from the timed steps: batch 2, ms_per_step
+        assert j["value"] == pytest.approx(2 * 1e3 / j["ms_per_step"],
+                                           rel=1e-2)
+    assert "ttft_ms" not in plain and "step_samples_ms" not in plain
+    assert full["ttft_ms"] > 0 and len(full["ttft_samples_ms"]) == 5
+    assert len(full["step_samples_ms"]) == 3
+
+    vocab = CFG["vocab_size"]
+    for d in (a, b):
+        assert sorted(p.name for p in d.iterdir()) == [
+            "logits.npy", "logits_columns.npy", "tokens.npy"]
+    ta, la = np.load(a / "tokens.npy"), np.load(a / "logits.npy")
+    assert ta.dtype == np.float64 and ta.shape == (1, 2)
+    assert la.dtype == np.float32 and la.shape == (1, 2, vocab)
+    assert np.isfinite(la).all()
+    # the dumped tokens are the greedy sample of the dumped logits
+    picked = np.take_along_axis(la, ta.astype(np.int64)[..., None], -1)
+    assert (picked[..., 0] == la.max(-1)).all()
+    assert (np.load(a / "logits_columns.npy") == np.arange(vocab)).all()
+    assert (ta == np.load(b / "tokens.npy")).all()
+    assert (la == np.load(b / "logits.npy")).all()
+
+
 DS_CFG = dict(model_type="deepseek_v2", hidden_size=64, num_hidden_layers=3,
               num_attention_heads=4, num_key_value_heads=4, vocab_size=128,
               intermediate_size=128, kv_lora_rank=32, qk_nope_head_dim=16,
