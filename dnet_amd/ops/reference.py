@@ -320,7 +320,10 @@ def rope_append(q, k, v, kcache, vcache, pos, cos, sin,
     B = q.shape[0]
     positions = pos.long()
     q.copy_(rope_apply(q, cos, sin, positions))
-    k.copy_(rope_apply(k, cos, sin, positions))
+    # like the kernel, quantize the f32 rotation, not its bf16 rounding
+    # (that would add up to 0.25 of a code step and shift the scale)
+    kf = rope_apply(k.float(), cos, sin, positions)
+    k.copy_(kf)
     q8 = kcache.dtype == torch.int8
     smax = kcache.shape[2]
     for b in range(B):
@@ -328,7 +331,7 @@ def rope_append(q, k, v, kcache, vcache, pos, cos, sin,
         if p < 0 or p >= smax:
             continue
         if q8:
-            kc, ks = quantize_kv_rows(k[b])
+            kc, ks = quantize_kv_rows(kf[b])
             vc, vs = quantize_kv_rows(v[b])
             kcache[b, :, p] = kc
             kscale[b, :, p] = ks

@@ -736,6 +736,8 @@ def test_fused_qkv_rope_matches_separate(kvq):
     kc2, vc2, ks2, vs2 = mkkv()
     qf = ops.gemv_qkv_rope(y, qp, scales, 128, 8, bias, nq, nkv, d,
                            kc2, vc2, pos, cos, sin, ks2, vs2)
+    assert int((_get_scratch(dev) != 0).sum()) == 0, \
+        "scratch not re-zeroed by rope_append_f32"
     assert torch.allclose(qf.float().cpu(), qr.float().cpu(), atol=3e-2,
                           rtol=2e-2), (qf.float() - qr.float()).abs().max()
     # the fused path quantizes/rounds from the f32 scratch (more precise
