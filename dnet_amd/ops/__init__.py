@@ -106,6 +106,9 @@ def gemv_bf16(x: torch.Tensor, w: torch.Tensor,
 def gemv_int8(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
               group: int, bias: torch.Tensor | None = None,
               packed: bool = False) -> torch.Tensor:
+    """Two weight contracts: the MFMA path (packed, M > 2) and the CPU
+    reference multiply by bf16(q*s); the scalar kernel (M <= 2, or unpacked
+    weights at any M) multiplies by the unrounded q*s."""
     if x.is_cuda:
         out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
         if packed and x.shape[0] > 2:

@@ -55,6 +55,13 @@ __global__ void gemv_bf16_kernel(const short* __restrict__ x,
   }
 }
 
+// Weight contract: this kernel multiplies by the UNROUNDED product q*s
+// (exact in f32). gemm_m16's deq8/deq4, dequant_int8 and the CPU reference
+// round q*s to bf16 first, so M <= 2 and M >= 3 are two slightly different
+// GEMMs on the same weights (up to 2^-8 relative per weight). Kept as is:
+// each path is tested against its own contract (docs/KERNELS.md, "How the
+// GEMMs are tested"); what the extra rounding would cost here is unmeasured.
+//
 // PACKED: weights in pack_int8_mfma chunk-pair order — the dot is
 // order-independent, so only the x vector indices change (vec i covers
 // orig k = pr*64 + sl*8 (+32): pr = i/4, sl = i%4).
