@@ -249,34 +249,44 @@ __global__ void gemm_m16_kernel(const short* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------
-// Streamed int8/int4 schedule (round-2).
+// Streamed int8/int4 schedule: a two-stage software pipeline over XT-k
+// x tiles (profiles/r03_gemm_pipeline.md).
 //
-// The generic kernel above is pair-rate bound on quantized weights: PMC
-// showed SQ_WAIT 69% with int8 wall time == bf16 wall time at every shape
-// (profiles/r01_gemm_ubench.md) — hipcc keeps only ~2 weight loads in
-// flight and serializes the x staging as load;vmcnt(0);ds_write per chunk
-// (one full round trip per 16-byte chunk). Per 256-k x-tile this schedule
-// instead takes ONE combined round trip:
+//   prologue: stage tile 0 (global_load_lds DMA) + load its weights, drain
+//   per tile i:
+//     raw s_barrier (lgkmcnt only)  — publishes tile i (every wave drained
+//                                     its share of the DMA before arriving)
+//                                     and retires tile i-1's readers
+//     issue tile i+1: x DMA into the OTHER image buffer, weights + scales
+//                     by plain loads into a second register set
+//     consume tile i from LDS/registers: A fragments of pair u+1 are
+//                     requested before the MFMAs of pair u, the dequant of
+//                     pair u+1 runs beside them (counted lgkmcnt waits)
+//     s_waitcnt vmcnt(0)            — tile i+1's DMA and weights, one drain
 //
-//   raw s_barrier (lgkmcnt only — previous tile's consumers done)
-//   issue x staging as global_load_lds DMA (no VGPR round trip)
-//   ONE asm block: issue the tile's weight+scale loads, s_waitcnt vmcnt(0)
-//   raw s_barrier
-//   dequant + MFMA from registers (no VMEM waits at all)
+// So a wave's global round trip overlaps its own MFMA work, one barrier
+// per tile replaces two, and a span remainder (64/128/192 k) runs through
+// the same stages as a short last tile with its pairs predicated by a
+// block-uniform count.
 //
-// The weight loads and the staging DMA are all in flight together
-// (10-14 VMEM ops, 5-9 KB per lane-group), so their latencies overlap in
-// one drain; wave overlap (4 blocks x 4 waves / CU) covers the per-wave
-// consume phase. Every async VMEM value is produced AND waited for
-// INSIDE a single asm statement: hipcc models asm outputs as ready when
-// the statement ends, so an async result that escapes a statement before
-// its s_waitcnt can be copied/rematerialized from an in-flight register
-// (measured: garbage numerics and corrupted-address page faults from the
-// earlier cross-tile ping-pong prefetch). Outputs are early-clobber so
-// the in-flight destinations can never alias the address operands.
+// The weight loads are plain C++ loads: hipcc counts them itself, so the
+// values may live across the loop back-edge (an inline-asm load may not:
+// hipcc treats asm outputs as ready when the statement ends, and an
+// in-flight destination can then be copied or reused — measured garbage
+// and page faults in round 2). sched_barrier(0) fences keep the loads in
+// front of the consume and their first use behind it.
 //
-// glds writes LDS at (wave-uniform base + lane*16), so the LDS x image is
-// UNPADDED (16*MT rows x 32 16B-chunks); bank conflicts on the 16-lane
+// Every wait hipcc has to know about is the s_waitcnt BUILTIN, not inline
+// asm, and the DMA is issued from inline asm, not the builtin (it has no
+// register destination, so nothing in flight escapes the statement):
+// hipcc keeps its own counters, and both a wait it cannot see and an
+// LDS-DMA it can see make it turn the counted lgkmcnt waits of the consume
+// back into lgkmcnt(0) between the MFMAs (see stage_tile and the kernel).
+// The tile loop is unrolled by two so the register sets swap without
+// copies.
+//
+// glds writes LDS at (wave-uniform base + lane*16), so an image is
+// UNPADDED (16*MT rows x XT/8 16B-chunks); bank conflicts on the 16-lane
 // fragment reads are killed by an XOR swizzle applied on the SOURCE
 // address instead of row padding (guide §5 rule 21): source chunk c lands
 // at image chunk c ^ (row & 15) — the 16 reader lanes (rows 0..15, same
@@ -285,238 +295,170 @@ __global__ void gemm_m16_kernel(const short* __restrict__ x,
 
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 
-// NSC = scales per 256-k tile = 256/G (G compile-time via dispatch; the
-// host streams only G in {64,128}, and requires the split start k to be
-// G-aligned so the in-tile scale index u*NSC/4 is exact).
-template <int QBITS, int NSC>
+// s_waitcnt immediate (gfx9 encoding): vmcnt(0), expcnt and lgkmcnt free
+constexpr int kWaitVm0 = 0x0F70;
+// lgkmcnt(0), vmcnt and expcnt free
+constexpr int kWaitLgkm0 = 0xC07F;
+
+// One tile's weights and scales. G is compile-time via dispatch (the host
+// streams only G in {64,128} and requires every split start to be
+// G-aligned, so pair u of a tile reads scale u*64/G).
+template <int QBITS, int G, int XT>
 struct WSet {
-  i32x4 w[QBITS == 8 ? 4 : 2];
-  unsigned s[NSC];
+  static constexpr int NW = QBITS == 8 ? XT / 64 : XT / 128;
+  static constexpr int NS = XT / G;
+  i32x4 w[NW];
+  unsigned s[NS];
 };
 
-// Load one tile's weights+scales and drain: single asm statement (see
-// header comment). wb already includes the lane's row offset
-// (n_w*K + woff) plus the tile's k byte offset; sb points at the tile's
-// first scale.
-template <int QBITS, int NSC>
-__device__ __forceinline__ void wset_load(WSet<QBITS, NSC>& o,
-                                          const void* wb, const short* sb) {
-  if constexpr (QBITS == 8 && NSC == 2) {
-    asm volatile(
-        "global_load_dwordx4 %0, %6, off\n\t"
-        "global_load_dwordx4 %1, %6, off offset:64\n\t"
-        "global_load_dwordx4 %2, %6, off offset:128\n\t"
-        "global_load_dwordx4 %3, %6, off offset:192\n\t"
-        "global_load_ushort %4, %7, off\n\t"
-        "global_load_ushort %5, %7, off offset:2\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(o.w[0]), "=&v"(o.w[1]), "=&v"(o.w[2]), "=&v"(o.w[3]),
-          "=&v"(o.s[0]), "=&v"(o.s[1])
-        : "v"(wb), "v"(sb)
-        : "memory");
-  } else if constexpr (QBITS == 8 && NSC == 4) {
-    asm volatile(
-        "global_load_dwordx4 %0, %8, off\n\t"
-        "global_load_dwordx4 %1, %8, off offset:64\n\t"
-        "global_load_dwordx4 %2, %8, off offset:128\n\t"
-        "global_load_dwordx4 %3, %8, off offset:192\n\t"
-        "global_load_ushort %4, %9, off\n\t"
-        "global_load_ushort %5, %9, off offset:2\n\t"
-        "global_load_ushort %6, %9, off offset:4\n\t"
-        "global_load_ushort %7, %9, off offset:6\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(o.w[0]), "=&v"(o.w[1]), "=&v"(o.w[2]), "=&v"(o.w[3]),
-          "=&v"(o.s[0]), "=&v"(o.s[1]), "=&v"(o.s[2]), "=&v"(o.s[3])
-        : "v"(wb), "v"(sb)
-        : "memory");
-  } else {
-    static_assert(QBITS == 4 && NSC == 2, "unsupported stream variant");
-    asm volatile(
-        "global_load_dwordx4 %0, %4, off\n\t"
-        "global_load_dwordx4 %1, %4, off offset:64\n\t"
-        "global_load_ushort %2, %5, off\n\t"
-        "global_load_ushort %3, %5, off offset:2\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(o.w[0]), "=&v"(o.w[1]), "=&v"(o.s[0]), "=&v"(o.s[1])
-        : "v"(wb), "v"(sb)
-        : "memory");
+// Issue one tile's weight + scale loads (plain loads, no wait here). wb is
+// the lane's row pointer (n_w row + woff) advanced to the tile; sb points
+// at the tile's first scale. A short tile (FULL = false) loads only what
+// its np pairs cover: the rest would lie past the row's end.
+template <int QBITS, int G, int XT, bool FULL>
+__device__ __forceinline__ void wset_load(WSet<QBITS, G, XT>& o,
+                                          const char* wb,
+                                          const unsigned short* sb,
+                                          const int np) {
+  constexpr int PPW = QBITS == 8 ? 1 : 2;  // pairs per 16-byte load
+#pragma unroll
+  for (int v = 0; v < WSet<QBITS, G, XT>::NW; ++v) {
+    if (FULL || v * PPW < np)
+      o.w[v] = *reinterpret_cast<const i32x4*>(wb + v * 64);
+    else
+      o.w[v] = i32x4{0, 0, 0, 0};
   }
+#pragma unroll
+  for (int j = 0; j < WSet<QBITS, G, XT>::NS; ++j)
+    o.s[j] = (FULL || j * G < np * 64) ? (unsigned)sb[j] : 0u;
 }
 
-// 2-tile weight batch: one statement issues BOTH tiles' weights (+ the
-// first tile's staging already in flight) and drains once — halves the
-// exposed weight round trips vs per-tile loads. Values are final at the
-// statement end, so holding tile B's registers across tile A's consume
-// and tile B's staging is safe (only IN-FLIGHT values must not escape).
-template <int QBITS, int NSC>
-struct WSet2 {
-  i32x4 w[QBITS == 8 ? 8 : 4];
-  unsigned s[2 * NSC];
-};
-
-template <int QBITS, int NSC>
-__device__ __forceinline__ void wset_load2(WSet2<QBITS, NSC>& o,
-                                           const void* wb, const short* sb) {
-  if constexpr (QBITS == 8 && NSC == 2) {
-    asm volatile(
-        "global_load_dwordx4 %0, %12, off\n\t"
-        "global_load_dwordx4 %1, %12, off offset:64\n\t"
-        "global_load_dwordx4 %2, %12, off offset:128\n\t"
-        "global_load_dwordx4 %3, %12, off offset:192\n\t"
-        "global_load_dwordx4 %4, %12, off offset:256\n\t"
-        "global_load_dwordx4 %5, %12, off offset:320\n\t"
-        "global_load_dwordx4 %6, %12, off offset:384\n\t"
-        "global_load_dwordx4 %7, %12, off offset:448\n\t"
-        "global_load_ushort %8, %13, off\n\t"
-        "global_load_ushort %9, %13, off offset:2\n\t"
-        "global_load_ushort %10, %13, off offset:4\n\t"
-        "global_load_ushort %11, %13, off offset:6\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(o.w[0]), "=&v"(o.w[1]), "=&v"(o.w[2]), "=&v"(o.w[3]),
-          "=&v"(o.w[4]), "=&v"(o.w[5]), "=&v"(o.w[6]), "=&v"(o.w[7]),
-          "=&v"(o.s[0]), "=&v"(o.s[1]), "=&v"(o.s[2]), "=&v"(o.s[3])
-        : "v"(wb), "v"(sb)
-        : "memory");
-  } else if constexpr (QBITS == 8 && NSC == 4) {
-    asm volatile(
-        "global_load_dwordx4 %0, %16, off\n\t"
-        "global_load_dwordx4 %1, %16, off offset:64\n\t"
-        "global_load_dwordx4 %2, %16, off offset:128\n\t"
-        "global_load_dwordx4 %3, %16, off offset:192\n\t"
-        "global_load_dwordx4 %4, %16, off offset:256\n\t"
-        "global_load_dwordx4 %5, %16, off offset:320\n\t"
-        "global_load_dwordx4 %6, %16, off offset:384\n\t"
-        "global_load_dwordx4 %7, %16, off offset:448\n\t"
-        "global_load_ushort %8, %17, off\n\t"
-        "global_load_ushort %9, %17, off offset:2\n\t"
-        "global_load_ushort %10, %17, off offset:4\n\t"
-        "global_load_ushort %11, %17, off offset:6\n\t"
-        "global_load_ushort %12, %17, off offset:8\n\t"
-        "global_load_ushort %13, %17, off offset:10\n\t"
-        "global_load_ushort %14, %17, off offset:12\n\t"
-        "global_load_ushort %15, %17, off offset:14\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(o.w[0]), "=&v"(o.w[1]), "=&v"(o.w[2]), "=&v"(o.w[3]),
-          "=&v"(o.w[4]), "=&v"(o.w[5]), "=&v"(o.w[6]), "=&v"(o.w[7]),
-          "=&v"(o.s[0]), "=&v"(o.s[1]), "=&v"(o.s[2]), "=&v"(o.s[3]),
-          "=&v"(o.s[4]), "=&v"(o.s[5]), "=&v"(o.s[6]), "=&v"(o.s[7])
-        : "v"(wb), "v"(sb)
-        : "memory");
-  } else {
-    static_assert(QBITS == 4 && NSC == 2, "unsupported stream variant");
-    asm volatile(
-        "global_load_dwordx4 %0, %8, off\n\t"
-        "global_load_dwordx4 %1, %8, off offset:64\n\t"
-        "global_load_dwordx4 %2, %8, off offset:128\n\t"
-        "global_load_dwordx4 %3, %8, off offset:192\n\t"
-        "global_load_ushort %4, %9, off\n\t"
-        "global_load_ushort %5, %9, off offset:2\n\t"
-        "global_load_ushort %6, %9, off offset:4\n\t"
-        "global_load_ushort %7, %9, off offset:6\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(o.w[0]), "=&v"(o.w[1]), "=&v"(o.w[2]), "=&v"(o.w[3]),
-          "=&v"(o.s[0]), "=&v"(o.s[1]), "=&v"(o.s[2]), "=&v"(o.s[3])
-        : "v"(wb), "v"(sb)
-        : "memory");
-  }
-}
-
-template <int MT, bool GLDS>
-__device__ __forceinline__ void stage_tile(const short* __restrict__ x,
-                                           short* x_lds, const int k0,
-                                           const int M, const int K) {
-  constexpr int NSG = MT * 2;  // glds per wave (1 KB each)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  asm volatile("s_barrier" ::: "memory");
+// Stage one x tile into an image. xk = x + tile start k (block-uniform);
+// offb[g] is the per-lane source BYTE offset of this wave's g-th 1 KB
+// slice (row clamp, swizzle: k-invariant, computed once per kernel).
+//
+// The DMA is issued from inline asm (it has no register destination, so
+// nothing in flight can escape the statement). Through the builtin hipcc
+// books every global_load_lds as a pending access to BOTH counters and
+// then turns each later wait into lgkmcnt(0)/vmcnt(0) until both have
+// drained: with a DMA in flight across the consume, that put a full
+// lgkmcnt(0) between the MFMAs again. LDS address = m0 + lane*16.
+template <int MT, int XT, bool GLDS>
+__device__ __forceinline__ void stage_tile(const short* __restrict__ xk,
+                                           short* img,
+                                           const unsigned (&offb)[MT * XT / 128]) {
+  constexpr int NSG = MT * XT / 128;  // 1 KB slices per wave
   const int wavei = (int)threadIdx.x >> 6, lanei = (int)threadIdx.x & 63;
   if constexpr (GLDS) {
+    const unsigned base = __builtin_amdgcn_readfirstlane(
+        (unsigned)(unsigned long)(__attribute__((address_space(3))) short*)img +
+        (unsigned)wavei * NSG * 1024u);
 #pragma unroll
-    for (int g = 0; g < NSG; ++g) {
-      const int L = (wavei * NSG + g) * 64 + lanei;  // image chunk
-      const int r = L >> 5;
-      const int cs = (L & 31) ^ (r & 15);            // source chunk (swizzle)
-      const short* ga = &x[(int64_t)min(r, M - 1) * K + k0 + cs * 8];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)ga,
-          (__attribute__((address_space(3))) void*)&x_lds[(wavei * NSG + g) *
-                                                          64 * 8],
-          16, 0, 0);
-    }
+    for (int g = 0; g < NSG; ++g)
+      asm volatile(
+          "s_mov_b32 m0, %0\n\t"
+          "s_nop 0\n\t"
+          "global_load_lds_dwordx4 %1, %2"
+          :
+          : "s"(base + g * 1024u), "v"(offb[g]), "s"(xk)
+          : "memory");
+    // DS ops bound-check against m0 on gfx9-family
+    asm volatile("s_mov_b32 m0, -1" ::: "memory");
   } else {
     // debug/fallback: same swizzled image via plain loads + ds_write
 #pragma unroll
-    for (int g = 0; g < NSG; ++g) {
-      const int L = (wavei * NSG + g) * 64 + lanei;
-      const int r = L >> 5;
-      const int cs = (L & 31) ^ (r & 15);
-      *reinterpret_cast<short8*>(&x_lds[L * 8]) =
-          *reinterpret_cast<const short8*>(
-              &x[(int64_t)min(r, M - 1) * K + k0 + cs * 8]);
-    }
+    for (int g = 0; g < NSG; ++g)
+      *reinterpret_cast<short8*>(&img[((wavei * NSG + g) * 64 + lanei) * 8]) =
+          *reinterpret_cast<const short8*>((const char*)xk + offb[g]);
   }
 }
 
-template <bool GLDS>
-__device__ __forceinline__ void end_stage() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  asm volatile("s_barrier" ::: "memory");
-  if constexpr (GLDS)  // DS ops bound-check against m0 on gfx9-family
-    asm volatile("s_mov_b32 m0, -1" ::: "memory");
-}
-
-// dequant + MFMA for one tile's 4 pairs from already-final registers
-template <int QBITS, int MT, int NSC>
-__device__ __forceinline__ void consume_tile(const i32x4* __restrict__ wv,
-                                             const unsigned* __restrict__ sc,
-                                             short* x_lds,
+// dequant + MFMA for one tile from already-final weight registers. The A
+// fragments of pair u+1 are requested before pair u's MFMAs, so only the
+// first pair's reads are waited on cold.
+template <int QBITS, int MT, int G, int XT, bool FULL>
+__device__ __forceinline__ void consume_tile(const WSet<QBITS, G, XT>& ws,
+                                             const short* img,
                                              f32x4 (&acc)[MT][2],
-                                             const int row, const int ks) {
-  const int ln4 = ks >> 3;  // lane>>4
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    bf16x8 b0, b1;
-    if (QBITS == 8) {
-      const int8_t* q8 = reinterpret_cast<const int8_t*>(&wv[u]);
-      const float sv = bits2f((short)sc[u * NSC / 4]);
-      b0 = deq8(q8, sv);
-      b1 = deq8(q8 + 8, sv);
-    } else {
-      const uint8_t* q4 =
-          reinterpret_cast<const uint8_t*>(&wv[u / 2]) + (u & 1) * 8;
-      const float sv = bits2f((short)sc[(u / 2) * NSC / 2]);
-      b0 = deq4(q4, sv);
-      b1 = deq4(q4 + 4, sv);
-    }
-    const int c0 = (u * 8 + ln4) ^ row;      // swizzled image chunks
-    const int c1 = (u * 8 + 4 + ln4) ^ row;
+                                             const int row, const int ln4,
+                                             const int np) {
+  constexpr int PT = XT / 64;
+  const short* rb = img + row * XT;
+  int v = ln4 ^ row;  // image chunk of source chunk c is c ^ row
+  // opaque: keeps the 2*PT swizzled read addresses of BOTH images from
+  // being hoisted out of the tile loop and held in registers throughout
+  asm volatile("" : "+v"(v));
+  bf16x8 a[2][MT][2];
+  bf16x8 b[2][2];
+  auto frag = [&](const int u, const int s) __attribute__((always_inline)) {
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
-      const short* rb = &x_lds[(t * 16 + row) * 256];
-      const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&rb[c0 * 8]);
-      const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&rb[c1 * 8]);
-      acc[t][0] =
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[t][0], 0, 0, 0);
-      acc[t][1] =
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[t][1], 0, 0, 0);
+      a[s][t][0] = *reinterpret_cast<const bf16x8*>(
+          &rb[t * 16 * XT + ((u * 8) ^ v) * 8]);
+      a[s][t][1] = *reinterpret_cast<const bf16x8*>(
+          &rb[t * 16 * XT + ((u * 8 + 4) ^ v) * 8]);
     }
+  };
+  auto deq = [&](const int u, const int s) __attribute__((always_inline)) {
+    const float sv = bits2f((short)ws.s[u * 64 / G]);
+    // opaque copy right at the use: without it the optimizer extracts the
+    // bytes of the whole register set a tile early (+48 VGPRs and spills)
+    i32x4 wq = ws.w[QBITS == 8 ? u : u / 2];
+    asm volatile("" : "+v"(wq));
+    if (QBITS == 8) {
+      const int8_t* q8 = reinterpret_cast<const int8_t*>(&wq);
+      b[s][0] = deq8(q8, sv);
+      b[s][1] = deq8(q8 + 8, sv);
+    } else {
+      const uint8_t* q4 = reinterpret_cast<const uint8_t*>(&wq) + (u & 1) * 8;
+      b[s][0] = deq4(q4, sv);
+      b[s][1] = deq4(q4 + 4, sv);
+    }
+  };
+  frag(0, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  deq(0, 0);
+#pragma unroll
+  for (int u = 0; u < PT; ++u) {
+    if (!FULL && u >= np) break;  // block-uniform
+    const int s = u & 1;
+    if (u + 1 < PT && (FULL || u + 1 < np)) frag(u + 1, s ^ 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (u + 1 < PT) deq(u + 1, s ^ 1);
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          a[s][t][0], b[s][0], acc[t][0], 0, 0, 0);
+      acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          a[s][t][1], b[s][1], acc[t][1], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// MINW: min waves per EU hint (occupancy/VGPR trade, see profiles/).
-template <int QBITS, int MT, int NSC, int MINW, bool GLDS = true>
+// XT: k per x tile; MINW: min waves per EU hint. Together with the LDS
+// size (two images) they pick the occupancy point per MT tier
+// (profiles/r03_gemm_pipeline.md).
+template <int QBITS, int MT, int G, int XT, int MINW, bool GLDS = true>
 __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
     const short* __restrict__ x, const void* __restrict__ w,
     const short* __restrict__ scales, const short* __restrict__ bias,
     short* __restrict__ out, float* __restrict__ out_f32, const int M,
-    const int K, const int N, const int G, const int splitk,
-    const int exact) {
-  constexpr int XT = 256;
-  __shared__ short x_lds[16 * MT * XT];  // unpadded (glds image, swizzled)
+    const int K, const int N, const int splitk, const int exact) {
+  using WS = WSet<QBITS, G, XT>;
+  constexpr int PT = XT / 64;
+  constexpr int CPR = XT / 8;         // 16-byte chunks per image row
+  constexpr int NSG = MT * XT / 128;  // 1 KB staging slices per wave
+  // two unpadded, swizzled glds images
+  constexpr int TILE = 16 * MT * XT;
+  __shared__ short x_lds[2 * TILE];
+  short* const x_img0 = x_lds;
+  short* const x_img1 = x_lds + TILE;
   const int wave = threadIdx.x / kWave;
   const int lane = threadIdx.x & (kWave - 1);
   const int n0 = (blockIdx.x * 4 + wave) * 16;
   const int row = lane & 15;
-  const int ks = (lane >> 4) * 8;
+  const int ln4 = lane >> 4;
   const int n_w = min(n0 + row, N - 1);
 
   const int pairs = K / 64;
@@ -531,7 +473,7 @@ __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
     p_begin = blockIdx.y * pp;
     p_end = (blockIdx.y == splitk - 1) ? pairs : p_begin + pp;
   }
-  const int woff = (lane >> 4) * 16;
+  const int woff = ln4 * 16;
 
   f32x4 acc[MT][2];
 #pragma unroll
@@ -539,97 +481,85 @@ __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
 #pragma unroll
     for (int u = 0; u < 2; ++u) acc[t][u] = {0.f, 0.f, 0.f, 0.f};
 
-  const void* wrow =
-      QBITS == 8
-          ? (const void*)((const int8_t*)w + (int64_t)n_w * K + woff)
-          : (const void*)((const uint8_t*)w + (int64_t)n_w * (K / 2) + woff);
-  const short* srow = scales + (int64_t)n_w * (K / G);
+  // bytes per k: int8 1, int4 1/2
+  const char* wrow = (const char*)w +
+                     (int64_t)n_w * (QBITS == 8 ? K : K / 2) + woff;
+  const unsigned short* srow =
+      (const unsigned short*)scales + (int64_t)n_w * (K / G);
 
   const int kbeg = p_begin * 64, kend = p_end * 64;
-  const int kfull = kbeg + ((kend - kbeg) / XT) * XT;
-  constexpr int GS = 256 / NSC;
-  int k0 = kbeg;
-  // 2-tile groups: one weight statement serves both tiles (one exposed
-  // round trip instead of two); tile B's staging waits alone
-  for (; k0 + 2 * XT <= kfull; k0 += 2 * XT) {
-    WSet2<QBITS, NSC> w2;
-    stage_tile<MT, GLDS>(x, x_lds, k0, M, K);
-    if (QBITS == 8)
-      wset_load2<QBITS, NSC>(w2, (const int8_t*)wrow + k0, srow + k0 / GS);
-    else
-      wset_load2<QBITS, NSC>(w2, (const uint8_t*)wrow + k0 / 2,
-                             srow + k0 / GS);
-    end_stage<GLDS>();
-    consume_tile<QBITS, MT, NSC>(&w2.w[0], &w2.s[0], x_lds, acc, row, ks);
-    stage_tile<MT, GLDS>(x, x_lds, k0 + XT, M, K);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // staging only
-    end_stage<GLDS>();
-    consume_tile<QBITS, MT, NSC>(&w2.w[QBITS == 8 ? 4 : 2], &w2.s[NSC],
-                                 x_lds, acc, row, ks);
-  }
-  for (; k0 < kfull; k0 += XT) {
-    WSet<QBITS, NSC> w1;
-    stage_tile<MT, GLDS>(x, x_lds, k0, M, K);
-    if (QBITS == 8)
-      wset_load<QBITS, NSC>(w1, (const int8_t*)wrow + k0, srow + k0 / GS);
-    else
-      wset_load<QBITS, NSC>(w1, (const uint8_t*)wrow + k0 / 2,
-                            srow + k0 / GS);
-    end_stage<GLDS>();
-    consume_tile<QBITS, MT, NSC>(&w1.w[0], &w1.s[0], x_lds, acc, row, ks);
+  const int nfull = (kend - kbeg) / XT;
+  const int rem = (kend - kbeg) - nfull * XT;  // 0, or 64..XT-64
+  const int ntiles = nfull + (rem > 0 ? 1 : 0);
+
+  // k-invariant staging source offsets (rows >= M read a clamped row;
+  // their C rows are never stored)
+  unsigned offb[NSG];
+#pragma unroll
+  for (int g = 0; g < NSG; ++g) {
+    const int L = (wave * NSG + g) * 64 + lane;  // image chunk
+    const int r = L / CPR;
+    const int cs8 = ((L % CPR) ^ (r & 15)) * 8;  // source k (swizzle)
+    offb[g] = 2u * (unsigned)(min(r, M - 1) * K + cs8);
   }
 
-  // tail (< XT k): generic serial staging + pair loop, executed by the
-  // whole block (condition uniform)
-  const int ln4 = ks >> 3;
-  for (; k0 < kend; k0 += XT) {
-    const int tk = kend - k0;  // < XT, multiple of 64
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    for (int idx = threadIdx.x; idx < 16 * MT * (tk / 8); idx += 256) {
-      const int r = idx / (tk / 8);
-      const int vec = idx % (tk / 8);
-      // same swizzled image as the glds path (rows are full 32-chunk
-      // strides even when tk < XT)
-      *reinterpret_cast<short8*>(&x_lds[(r * 32 + (vec ^ (r & 15))) * 8]) =
-          *reinterpret_cast<const short8*>(
-              &x[(int64_t)min(r, M - 1) * K + k0 + vec * 8]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    for (int pl = 0; pl < tk / 64; ++pl) {
-      const int p = (k0 / 64) + pl;
-      bf16x8 b0, b1;
-      if (QBITS == 8) {
-        const int8_t* wq = (const int8_t*)wrow;
-        const int4 wv = *reinterpret_cast<const int4*>(&wq[p * 64]);
-        const int8_t* q8 = reinterpret_cast<const int8_t*>(&wv);
-        const float sv = bits2f(srow[(p * 64) / G]);
-        b0 = deq8(q8, sv);
-        b1 = deq8(q8 + 8, sv);
-      } else {
-        const int quad = p / 2;
-        const int half = p & 1;
-        const uint8_t* wq = (const uint8_t*)wrow;
-        const int2 wv =
-            *reinterpret_cast<const int2*>(&wq[quad * 64 + half * 8]);
-        const uint8_t* q4 = reinterpret_cast<const uint8_t*>(&wv);
-        const float sv = bits2f(srow[(quad * 128) / G]);
-        b0 = deq4(q4, sv);
-        b1 = deq4(q4 + 4, sv);
-      }
-      const int c0 = (pl * 8 + ln4) ^ row;
-      const int c1 = (pl * 8 + 4 + ln4) ^ row;
+  // issue tile i: x image + weights. A short last tile clamps the source
+  // k into the tile (image columns past it hold junk and are never read)
+  // and loads only the pairs it has.
+  auto issue = [&](const int i, short* img, WS& dst)
+      __attribute__((always_inline)) {
+    const int k0 = kbeg + i * XT;
+    const char* wb = wrow + (QBITS == 8 ? k0 : k0 / 2);
+    if (i < nfull) {
+      stage_tile<MT, XT, GLDS>(x + k0, img, offb);
+      wset_load<QBITS, G, XT, true>(dst, wb, srow + k0 / G, PT);
+    } else {
+      unsigned offp[NSG];
 #pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        const short* rb = &x_lds[(t * 16 + row) * 256];
-        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&rb[c0 * 8]);
-        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&rb[c1 * 8]);
-        acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[t][0],
-                                                            0, 0, 0);
-        acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[t][1],
-                                                            0, 0, 0);
+      for (int g = 0; g < NSG; ++g) {
+        const int L = (wave * NSG + g) * 64 + lane;
+        const int r = L / CPR;
+        const int cs8 = ((L % CPR) ^ (r & 15)) * 8;
+        offp[g] = 2u * (unsigned)(min(r, M - 1) * K + min(cs8, rem - 8));
       }
+      stage_tile<MT, XT, GLDS>(x + k0, img, offp);
+      wset_load<QBITS, G, XT, false>(dst, wb, srow + k0 / G, rem / 64);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // one pipeline step: publish tile i, put tile i+1 in flight, consume i
+  auto step = [&](const int i, const short* img, short* img_next, WS& cur,
+                  WS& nxt) __attribute__((always_inline)) {
+    // raw barrier (lgkmcnt only): __syncthreads() would add a vmcnt(0)
+    // (the wait is the builtin so that hipcc's own counters see it: after
+    // an inline-asm wait it still believes the previous tile's reads are
+    // pending and turns every counted lgkmcnt in the consume into 0)
+    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+    asm volatile("s_barrier" ::: "memory");
+    if (i + 1 < ntiles) issue(i + 1, img_next, nxt);
+    if (i < nfull)
+      consume_tile<QBITS, MT, G, XT, true>(cur, img, acc, row, ln4, PT);
+    else
+      consume_tile<QBITS, MT, G, XT, false>(cur, img, acc, row, ln4,
+                                             rem / 64);
+    __builtin_amdgcn_sched_barrier(0);
+    // the DMA has no register destination for hipcc to wait on. The
+    // builtin, not inline asm: hipcc then knows the DMA has landed and
+    // does not drain vmcnt again before the next tile's first ds_read
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+  };
+
+  if (ntiles > 0) {  // block-uniform (a forced deep split can be empty)
+    WS wa, wb2;
+#pragma unroll
+    for (int v = 0; v < WS::NW; ++v) wb2.w[v] = i32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < WS::NS; ++j) wb2.s[j] = 0u;
+    issue(0, x_img0, wa);
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+    for (int i = 0; i < ntiles; i += 2) {
+      step(i, x_img0, x_img1, wa, wb2);
+      if (i + 1 < ntiles) step(i + 1, x_img1, x_img0, wb2, wa);
     }
   }
 
@@ -756,37 +686,31 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
   hipLaunchKernelGGL((gemm_m16_kernel<QQ, TT>), grid, dim3(256), 0, stream, \
                      xp, w.data_ptr(), sp, bp1, op, fp, M, (int)K, (int)N,  \
                      group, sk, exact)
-  static const bool mt4occ3 = []() {
-    const char* e = getenv("DNET_GEMM_MT4OCC");
-    return e == nullptr || e[0] == '3';  // default: spill-free 3-wave MT4
-  }();
   static const bool noglds = getenv("DNET_GEMM_NOGLDS") != nullptr;
-#define LAUNCH_STREAM(QQ, TT, NSC, MW)                                      \
+#define LAUNCH_STREAM(QQ, TT, GG, XT, MW)                                   \
   do {                                                                      \
     if (noglds)                                                             \
-      hipLaunchKernelGGL((gemm_m16_stream_kernel<QQ, TT, NSC, MW, false>), \
-                         grid, dim3(256), 0, stream, xp, w.data_ptr(), sp,  \
-                         bp1, op, fp, M, (int)K, (int)N, group, sk, exact); \
+      hipLaunchKernelGGL(                                                   \
+          (gemm_m16_stream_kernel<QQ, TT, GG, XT, 2, false>), grid,         \
+          dim3(256), 0, stream, xp, w.data_ptr(), sp, bp1, op, fp, M,       \
+          (int)K, (int)N, sk, exact);                                       \
     else                                                                    \
-      hipLaunchKernelGGL((gemm_m16_stream_kernel<QQ, TT, NSC, MW, true>),   \
-                         grid, dim3(256), 0, stream, xp, w.data_ptr(), sp,  \
-                         bp1, op, fp, M, (int)K, (int)N, group, sk, exact); \
+      hipLaunchKernelGGL(                                                   \
+          (gemm_m16_stream_kernel<QQ, TT, GG, XT, MW, true>), grid,         \
+          dim3(256), 0, stream, xp, w.data_ptr(), sp, bp1, op, fp, M,       \
+          (int)K, (int)N, sk, exact);                                       \
   } while (0)
-#define LAUNCH_STREAM_G8(TT)                                            \
-  do {                                                                    \
-    if (TT == 4 && mt4occ3) {                                             \
-      if (group == 64) LAUNCH_STREAM(8, TT, 4, 3);                        \
-      else LAUNCH_STREAM(8, TT, 2, 3);                                    \
-    } else {                                                              \
-      if (group == 64) LAUNCH_STREAM(8, TT, 4, 4);                        \
-      else LAUNCH_STREAM(8, TT, 2, 4);                                    \
-    }                                                                     \
+  // occupancy point per MT tier (profiles/r03_gemm_pipeline.md)
+  // occupancy point per MT tier (profiles/r03_gemm_pipeline.md): 256-k
+  // tiles everywhere; two 32 KB images leave MT4 two blocks per CU
+#define LAUNCH_STREAM_T(QQ, TT, GG) \
+  LAUNCH_STREAM(QQ, TT, GG, 256, (TT == 4 ? 2 : TT == 2 ? 3 : 4))
+#define LAUNCH_STREAM_G8(TT)                                                \
+  do {                                                                      \
+    if (group == 64) LAUNCH_STREAM_T(8, TT, 64);                            \
+    else LAUNCH_STREAM_T(8, TT, 128);                                       \
   } while (0)
-#define LAUNCH_STREAM_G4(TT)                                              \
-  do {                                                                    \
-    if (TT == 4 && mt4occ3) LAUNCH_STREAM(4, TT, 2, 3);                   \
-    else LAUNCH_STREAM(4, TT, 2, 4);                                      \
-  } while (0)
+#define LAUNCH_STREAM_G4(TT) LAUNCH_STREAM_T(4, TT, 128)
   // the streamed counted-vmcnt schedule needs a compile-time scale count
   // per 256-k tile; other group sizes fall back to the generic kernel
   // G must divide every tile start (k0 is any multiple of 64 under
@@ -816,6 +740,7 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
   }
 #undef LAUNCH
 #undef LAUNCH_STREAM
+#undef LAUNCH_STREAM_T
 #undef LAUNCH_STREAM_G8
 #undef LAUNCH_STREAM_G4
   if (sk > 1) {
