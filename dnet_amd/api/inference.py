@@ -26,6 +26,20 @@ from .tokenizer import Detokenizer
 log = get_logger("api")
 
 
+def decoding_params(request: ChatRequestModel) -> dict:
+    """The `params` dict of an infer request: every sampling control the
+    shard runtime understands."""
+    return {
+        "seed": request.seed,
+        "temperature": request.temperature, "top_p": request.top_p,
+        "top_k": request.top_k, "min_p": request.min_p,
+        "repetition_penalty": request.repetition_penalty,
+        "presence_penalty": request.presence_penalty,
+        "frequency_penalty": request.frequency_penalty,
+        "logprobs": request.logprobs,
+        "top_logprobs": request.top_logprobs}
+
+
 class InferenceManager:
     def __init__(self, model_manager, token_timeout_s: float = 300.0):
         self.mm = model_manager
@@ -106,12 +120,7 @@ class InferenceManager:
                 "tokens": np.asarray(prompt_ids, dtype=np.int32).tobytes(),
                 "prompt_len": len(prompt_ids),
                 "max_tokens": request.effective_max_tokens,
-                "params": {
-                    "seed": request.seed,
-                    "temperature": request.temperature, "top_p": request.top_p,
-                    "top_k": request.top_k, "min_p": request.min_p,
-                    "logprobs": request.logprobs,
-                    "top_logprobs": request.top_logprobs},
+                "params": decoding_params(request),
                 "stop_ids": list(self.mm.stop_ids),
                 "callback": self.callback_addr})
             yield ChatChunkModel(id=nonce, model=request.model, choices=[

@@ -27,7 +27,11 @@ class ChatRequestModel(BaseModel):
     top_p: float = 1.0
     top_k: int = 0
     min_p: float = 0.0
-    repetition_penalty: float = 1.0
+    # HF/vLLM multiplicative penalty (> 0) and the two OpenAI additive
+    # ones (range [-2, 2]); out of range is a 422
+    repetition_penalty: float = Field(default=1.0, gt=0.0)
+    presence_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
+    frequency_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
     stream: bool = False
     stop: Optional[list[str] | str] = None
     logprobs: bool = False

@@ -99,6 +99,12 @@ class ObsSettings(BaseModel):
     sync_every_n: int = 0
 
 
+class SamplingSettings(BaseModel):
+    # DNET_FUSED_SAMPLER=0 keeps batched sampling on the torch
+    # sort/softmax path on GPU instead of the fused HIP sampler
+    fused_sampler: bool = True
+
+
 class DnetSettings(BaseModel):
     logging: LoggingSettings = Field(default_factory=LoggingSettings)
     api: ApiSettings = Field(default_factory=ApiSettings)
@@ -109,6 +115,7 @@ class DnetSettings(BaseModel):
     storage: StorageSettings = Field(default_factory=StorageSettings)
     topology: TopologySettings = Field(default_factory=TopologySettings)
     observability: ObsSettings = Field(default_factory=ObsSettings)
+    sampling: SamplingSettings = Field(default_factory=SamplingSettings)
 
 
 _PREFIXES = {
@@ -121,6 +128,7 @@ _PREFIXES = {
     "storage": "DNET_STORAGE_",
     "topology": "DNET_TOPOLOGY_",
     "observability": "DNET_OBS_",
+    "sampling": "DNET_",
 }
 
 

@@ -1,4 +1,5 @@
-"""Token sampling: temperature / top-k / top-p / min-p + logprobs.
+"""Token sampling: repetition / presence / frequency penalties,
+temperature / top-k / top-p / min-p + logprobs.
 
 Reference counterpart: src/dnet/core/decoding/sampler.py (mlx_lm
 make_sampler); here implemented on torch logits [B, V].
@@ -19,6 +20,31 @@ class DecodingConfig:
     min_p: float = 0.0
     logprobs: bool = False
     top_logprobs: int = 0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    @property
+    def has_penalty(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0)
+
+
+def new_seen_table(rows: int, vocab: int, device=None) -> torch.Tensor:
+    """Per-row token history for the penalties: bits 0..29 count how often
+    the request generated the token, bit 30 marks prompt tokens."""
+    return torch.zeros(rows, vocab, dtype=torch.int32, device=device)
+
+
+def mark_prompt(seen_row: torch.Tensor, tokens) -> None:
+    idx = torch.as_tensor(tokens, dtype=torch.long,
+                          device=seen_row.device).reshape(-1)
+    seen_row[idx] |= _ops().ref.SEEN_PROMPT_BIT
+
+
+def _ops():
+    from .. import ops
+    return ops
 
 
 class Sampler:
@@ -27,11 +53,25 @@ class Sampler:
         self.cfg = cfg or DecodingConfig()
         self.generator = generator
 
-    def sample(self, logits: torch.Tensor):
+    def sample(self, logits: torch.Tensor, seen: torch.Tensor | None = None):
         """logits [B, V] -> (tokens [B] int64, logprob [B] or None,
-        top_logprobs list or None)."""
+        top_logprobs list or None). With a `seen` table [B, V] the
+        config's penalties shape the choice (logprobs stay on the raw
+        logits) and the returned tokens are counted in it."""
         c = self.cfg
         lf = logits.float()
+        raw = lf
+        if seen is not None and c.has_penalty:
+            lf = _ops().apply_penalties(lf, seen, c.repetition_penalty,
+                                        c.presence_penalty,
+                                        c.frequency_penalty)
+        tok = self._choose(lf)
+        if seen is not None:
+            _ops().count_tokens(seen, tok)
+        return self._logprobs(raw, tok)
+
+    def _choose(self, lf: torch.Tensor) -> torch.Tensor:
+        c = self.cfg
         if c.temperature <= 0.0:
             tok = lf.argmax(dim=-1)
         else:
@@ -61,28 +101,47 @@ class Sampler:
                 lf.nan_to_num(nan=0.0).argmax(dim=-1), lf.shape[-1]).float()
             probs = torch.where(ok, probs, fallback)
             tok = torch.multinomial(probs, 1, generator=self.generator).squeeze(-1)
+        return tok
+
+    def _logprobs(self, raw, tok):
+        """Logprobs of the raw (unpenalised) f32 logits."""
+        c = self.cfg
         if not c.logprobs:
             return tok, None, None
-        logp = lf - torch.logsumexp(lf, dim=-1, keepdim=True)
+        logp = raw - torch.logsumexp(raw, dim=-1, keepdim=True)
         chosen = logp.gather(-1, tok.unsqueeze(-1)).squeeze(-1)
         tops = None
         if c.top_logprobs:
             tv, ti = torch.topk(logp, c.top_logprobs, dim=-1)
             tops = [{int(i): float(v) for v, i in zip(tv[b], ti[b])}
-                    for b in range(logits.shape[0])]
+                    for b in range(raw.shape[0])]
         return tok, chosen, tops
 
 
 class RowSampler:
     """Per-row sampling for slot-batched serving: each row of the logits
     batch carries its own request's decoding params (temperature / top_k /
-    top_p / min_p), vectorized in one pass. Greedy rows (temperature 0)
-    take the argmax; sampled rows go through per-row filtered multinomial
-    with the same degenerate-row guard as ``Sampler``."""
+    top_p / min_p / penalties), vectorized in one pass. Greedy rows
+    (temperature 0) take the argmax. On GPU logits every other batch is one
+    launch of the fused HIP sampler (``ops.sample_rows``) on the bf16
+    logits; CPU logits, and GPU ones when ``DNET_FUSED_SAMPLER=0``, go
+    through per-row filtered multinomial with the same degenerate-row
+    guard as ``Sampler``."""
 
-    def __init__(self, batch: int, device=None):
+    def __init__(self, batch: int, device=None, vocab: int | None = None):
+        from ..config import get_settings
         self.batch = batch
+        self.vocab = vocab         # sizes the token-history table
         self.device = device
+        self.fused = bool(get_settings().sampling.fused_sampler)
+        # penalties: neutral rows cost nothing; the [batch, V] token
+        # history is allocated when the first penalised row is set
+        self.rep = torch.ones(batch, device=device)
+        self.pres = torch.zeros(batch, device=device)
+        self.freq = torch.zeros(batch, device=device)
+        self._pen_py = [False] * batch
+        self.seen: Optional[torch.Tensor] = None
+        self._u0 = None            # zeros: uniforms of an all-greedy batch
         self.temp = torch.zeros(batch, device=device)
         self.top_p = torch.ones(batch, device=device)
         self.top_k = torch.zeros(batch, dtype=torch.long, device=device)
@@ -107,6 +166,17 @@ class RowSampler:
         self._filt_py = [False] * batch
 
     def set_row(self, i: int, cfg: DecodingConfig, seed=None):
+        self.rep[i] = cfg.repetition_penalty
+        self.pres[i] = cfg.presence_penalty
+        self.freq[i] = cfg.frequency_penalty
+        self._pen_py[i] = cfg.has_penalty
+        if cfg.has_penalty and self.seen is None:
+            if self.vocab is None:
+                raise ValueError("penalties need RowSampler(vocab=...)")
+            self.seen = new_seen_table(self.batch, int(self.vocab),
+                                       self.device)
+        if self.seen is not None:
+            self.seen[i].zero_()
         self.temp[i] = cfg.temperature
         self.top_p[i] = cfg.top_p
         self.top_k[i] = cfg.top_k
@@ -131,11 +201,51 @@ class RowSampler:
         self.top_p[i] = 1.0
         self.top_k[i] = 0
         self.min_p[i] = 0.0
+        self.rep[i] = 1.0
+        self.pres[i] = 0.0
+        self.freq[i] = 0.0
+        self._pen_py[i] = False
         self._temp_py[i] = 0.0
         self._filt_py[i] = False
         self.want_lp[i] = False
         self.n_top[i] = 0
         self.gens[i] = None
+
+    def note_prompt(self, i: int, tokens) -> None:
+        """Mark row i's prompt tokens (after ``set_row``)."""
+        if self.seen is not None and self._pen_py[i]:
+            mark_prompt(self.seen[i], tokens)
+
+    def seen_rows(self, i: int):
+        """Row i of the token history as a [1, V] table for ``Sampler``,
+        or None when the row carries no penalty."""
+        if self.seen is not None and self._pen_py[i]:
+            return self.seen[i:i + 1]
+        return None
+
+    def reset_counts(self, i: int) -> None:
+        """Forget what row i was counted as generating, keep its prompt
+        marks. Every row of the batch is sampled and counted each step,
+        also a slot that is parked while its prompt prefills chunk by
+        chunk; call this before the slot's first real token."""
+        if self.seen is not None and self._pen_py[i]:
+            self.seen[i] &= _ops().ref.SEEN_PROMPT_BIT
+
+    def note_token(self, i: int, tok: int) -> None:
+        """Count a token of row i that was sampled elsewhere (the first
+        token of a slot comes from ``Sampler``)."""
+        if self.seen is not None and self._pen_py[i]:
+            _ops().count_tokens(self.seen[i:i + 1],
+                                torch.tensor([int(tok)], device=self.device))
+
+    def _uniforms(self, B, device):
+        # seeded rows draw from their own generator, so a request's stream
+        # depends on nothing but its seed
+        u = torch.rand(B, 1, device=device)
+        for i, g in enumerate(self.gens[:B]):
+            if g is not None:
+                u[i] = torch.rand(1, 1, device=device, generator=g)
+        return u
 
     def _logprobs_for(self, lf, tok):
         B = lf.shape[0]
@@ -152,14 +262,47 @@ class RowSampler:
             self.last_logp = self.last_topv = self.last_topi = None
 
     def sample(self, logits: torch.Tensor) -> torch.Tensor:
-        lf = logits.float()
-        B, V = lf.shape
+        B, V = logits.shape
+        pen = any(self._pen_py[:B])
+        sampled = any(t > 0 for t in self._temp_py[:B])
+        if logits.is_cuda and self.fused and (pen or sampled):
+            # one launch over the bf16 logits: penalties, temperature,
+            # filters and the draw, sort-free
+            tok = _ops().sample_rows(
+                logits, self.temp, self.top_k, self.top_p, self.min_p,
+                self._uniforms(B, logits.device) if sampled else self._zeros(),
+                self.rep if pen else None, self.pres if pen else None,
+                self.freq if pen else None, self.seen if pen else None)
+            if any(self.want_lp[:B]):
+                self._logprobs_for(logits.float(), tok)
+            else:
+                self.last_logp = self.last_topv = self.last_topi = None
+            return tok
+        raw = lf = logits.float()
+        if pen:
+            lf = _ops().apply_penalties(lf, self.seen, self.rep, self.pres,
+                                        self.freq)
+        tok = self._sample_torch(lf, raw, B, V)
+        if pen:
+            _ops().count_tokens(self.seen[:B], tok)
+        return tok
+
+    def _zeros(self):
+        # all-greedy penalised batch: the kernel reads no uniform
+        if self._u0 is None:
+            self._u0 = torch.zeros(self.batch, device=self.device)
+        return self._u0
+
+    def _sample_torch(self, lf, raw, B, V):
+        """Torch path over (penalised) f32 logits `lf`; logprobs are taken
+        from the raw logits."""
         greedy_tok = lf.argmax(dim=-1)
         # fast path: every row greedy (the common serving batch) — the
         # full sort/softmax/multinomial over [B, V] cost ~25 ms/step on
-        # a 152k vocab and collapsed serving throughput 4x
+        # a 152k vocab and collapsed serving throughput 4x (today's stack
+        # measures 1.0-1.8 ms for it: profiles/r04_fused_sampler.md)
         if not any(t > 0 for t in self._temp_py[:B]):
-            self._logprobs_for(lf, greedy_tok)
+            self._logprobs_for(raw, greedy_tok)
             return greedy_tok
         t = self.temp.clamp_min(1e-6).unsqueeze(-1)
         x = lf / t
@@ -172,8 +315,8 @@ class RowSampler:
                 lf.nan_to_num(nan=0.0).argmax(dim=-1), V).float()
             probs = torch.where(ok, probs, fallback)
             tok = self._draw(probs, B, V, lf.device)
-            tok = torch.where(self.temp <= 0.0, greedy_tok, tok)
-            self._logprobs_for(lf, tok)
+            tok = torch.where(self.temp[:B] <= 0.0, greedy_tok, tok)
+            self._logprobs_for(raw, tok)
             return tok
         sx, si = torch.sort(x, descending=True, dim=-1)
         ranks = torch.arange(V, device=lf.device).expand(B, V)
@@ -199,8 +342,8 @@ class RowSampler:
             lf.nan_to_num(nan=0.0).argmax(dim=-1), V).float()
         probs = torch.where(ok, probs, fallback)
         tok = self._draw(probs, B, V, lf.device)
-        tok = torch.where(self.temp <= 0.0, greedy_tok, tok)
-        self._logprobs_for(lf, tok)
+        tok = torch.where(self.temp[:B] <= 0.0, greedy_tok, tok)
+        self._logprobs_for(raw, tok)
         return tok
 
     def _draw(self, probs, B, V, device):

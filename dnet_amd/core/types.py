@@ -45,6 +45,8 @@ class DecodingParams(BaseModel):
     top_k: int = 0
     min_p: float = 0.0
     repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
     logprobs: bool = False
     top_logprobs: int = 0
 

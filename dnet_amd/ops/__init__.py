@@ -407,6 +407,32 @@ rope_tables = ref.rope_tables
 rope_apply = ref.rope_apply
 mxfp4_dequant = ref.mxfp4_dequant
 quantize_mxfp4 = ref.quantize_mxfp4
+apply_penalties = ref.apply_penalties
+count_tokens = ref.count_tokens
+
+
+def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
+                top_k: torch.Tensor, top_p: torch.Tensor,
+                min_p: torch.Tensor, u: torch.Tensor, rep=None, pres=None,
+                freq=None, seen: torch.Tensor | None = None,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """Fused per-row sampler: logits [B, V] (bf16 or f32, row stride >= V)
+    -> tokens [B] int64. Per-row temp / top_k / top_p / min_p and a uniform
+    u in [0, 1); optional rep / pres / freq penalties over the int32 `seen`
+    table [>= B, V], whose count for the returned token is incremented. The
+    parameter tensors may be longer than B. One launch on the current
+    stream, no host sync; semantics in ``reference.sample_rows``."""
+    if logits.is_cuda:
+        B = logits.shape[0]
+        if out is None:
+            out = torch.empty(B, dtype=torch.int64, device=logits.device)
+        if top_k.dtype != torch.int64:
+            top_k = top_k.to(torch.int64)
+        _native().sample_rows(logits, temp, top_k, top_p, min_p, rep, pres,
+                              freq, seen, u.reshape(-1), out)
+        return out[:B]
+    return ref.sample_rows(logits, temp, top_k, top_p, min_p, u, rep, pres,
+                           freq, seen)
 
 
 def dequant_mxfp4(w: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:

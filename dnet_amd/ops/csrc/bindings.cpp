@@ -65,6 +65,13 @@ void moe_down(torch::Tensor act, torch::Tensor w,
 void col_norm2(torch::Tensor x, torch::Tensor norms);
 void gather_cols(torch::Tensor x, torch::Tensor idx, torch::Tensor out);
 void scatter_cols(torch::Tensor in, torch::Tensor idx, torch::Tensor out);
+void sample_rows(torch::Tensor logits, torch::Tensor temp, torch::Tensor top_k,
+                 torch::Tensor top_p, torch::Tensor min_p,
+                 c10::optional<torch::Tensor> rep,
+                 c10::optional<torch::Tensor> pres,
+                 c10::optional<torch::Tensor> freq,
+                 c10::optional<torch::Tensor> seen, torch::Tensor u,
+                 torch::Tensor out_tok);
 }  // namespace dnet
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -118,4 +125,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("col_norm2", &dnet::col_norm2, "per-column L2 norms");
   m.def("gather_cols", &dnet::gather_cols, "pack kept columns");
   m.def("scatter_cols", &dnet::scatter_cols, "zero + scatter kept columns");
+  m.def("sample_rows", &dnet::sample_rows,
+        "fused per-row penalties + temperature + top-k/top-p/min-p + draw",
+        py::arg("logits"), py::arg("temp"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("min_p"), py::arg("rep"), py::arg("pres"), py::arg("freq"),
+        py::arg("seen"), py::arg("u"), py::arg("out_tok"));
 }

@@ -474,3 +474,108 @@ def attn_combine(partials: torch.Tensor,
     num = (acc * w.unsqueeze(-1)).sum(2)
     denom = denom.clamp_min(1e-30)
     return (num / denom.unsqueeze(-1)).to(torch.bfloat16)
+
+
+# --- token sampling -------------------------------------------------------
+# `seen` [B, V] int32: bits 0..29 count how often the request generated the
+# token, bit 30 says the token occurs in the prompt.
+SEEN_COUNT_MASK = 0x3FFFFFFF
+SEEN_PROMPT_BIT = 0x40000000
+
+
+def apply_penalties(lf: torch.Tensor, seen: torch.Tensor, rep, pres,
+                    freq) -> torch.Tensor:
+    """HF/vLLM repetition, frequency and presence penalties on raw f32
+    logits [B, V]. rep/pres/freq are floats or [B] tensors; `seen` may
+    have more rows than `lf`. Works on any device."""
+    B = lf.shape[0]
+
+    def col(v):
+        if torch.is_tensor(v):
+            return v[:B].to(lf.device, torch.float32).unsqueeze(-1)
+        return torch.full((B, 1), float(v), dtype=torch.float32,
+                          device=lf.device)
+
+    rep, pres, freq = col(rep), col(pres), col(freq)
+    s = seen[:B]
+    c = s & SEEN_COUNT_MASK
+    hit = ((c > 0) | ((s & SEEN_PROMPT_BIT) != 0)) & (rep != 1.0)
+    lf = torch.where(hit, torch.where(lf > 0, lf / rep, lf * rep), lf)
+    lf = lf - freq * c.float()
+    return torch.where(c > 0, lf - pres, lf)
+
+
+def count_tokens(seen: torch.Tensor, tok: torch.Tensor) -> None:
+    """seen[b, tok[b]] += 1, saturating in bits 0..29."""
+    rows = torch.arange(tok.shape[0], device=seen.device)
+    w = seen[rows, tok]
+    seen[rows, tok] = torch.where((w & SEEN_COUNT_MASK) == SEEN_COUNT_MASK,
+                                  w, w + 1)
+
+
+def _sample_row(l: torch.Tensor, temp: float, top_k: int, top_p: float,
+                min_p: float, u: float) -> int:
+    """One row of penalised f32 logits -> token (see sample_rows)."""
+    V = l.shape[0]
+    nan = torch.isnan(l)
+    lv = torch.where(nan, torch.full_like(l, float("-inf")), l)
+    lmax = lv.max()
+    if lmax == float("-inf"):        # no finite value: argmax(nan_to_num)
+        return int(nan.nonzero()[0]) if bool(nan.any()) else 0
+    first_max = int((lv == lmax).nonzero()[0])
+    if not temp > 0.0 or lmax == float("inf"):
+        return first_max
+    a = (lv - lmax) / torch.tensor(temp, dtype=torch.float32)
+    e = torch.exp(a)
+    e64 = e.double()
+    keep = ~nan
+    if 0 < top_k < V:
+        kth = torch.topk(a[~nan], min(top_k, int((~nan).sum()))).values[-1]
+        keep &= a >= kth
+    if top_p < 1.0:
+        sa, si = torch.sort(a, descending=True, stable=True)
+        se = e64[si]
+        cum_excl = se.cumsum(0) - se
+        first = torch.searchsorted(-sa, -sa, right=False)  # head of tie class
+        above = torch.empty_like(cum_excl)
+        above[si] = cum_excl[first]
+        pT = max(float(torch.tensor(top_p, dtype=torch.float32)), 0.0) \
+            * float(e64.sum())
+        keep &= (above < pT) | (a == 0)      # the max token is always kept
+    if min_p > 0.0:
+        keep &= e >= torch.tensor(min(min_p, 1.0), dtype=torch.float32)
+    cdf = torch.where(keep, e64, torch.zeros_like(e64)).cumsum(0)
+    S = float(cdf[-1])
+    tok = int(torch.searchsorted(
+        cdf, torch.tensor(max(u, 0.0) * S, dtype=torch.float64), right=True))
+    return tok if tok < V and bool(keep[tok]) else first_max
+
+
+def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
+                top_k: torch.Tensor, top_p: torch.Tensor,
+                min_p: torch.Tensor, u: torch.Tensor, rep=None, pres=None,
+                freq=None, seen: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-row sampling, the contract of the fused HIP sampler.
+
+    Penalties act on the raw f32 logit (rows of `seen`), `temp <= 0` rows
+    take the argmax (lowest index on ties). Otherwise with
+    x = l / temp, e = exp(x - max x), T = sum e, token i is kept iff
+    fewer than top_k tokens have a larger x, the mass of larger-x tokens
+    is below top_p * T, and e_i >= min_p; equal values share their fate.
+    The token is the smallest kept index whose inclusive kept-mass prefix
+    exceeds u * S. When `seen` is given the returned token is counted."""
+    B = logits.shape[0]
+    lf = logits.float()
+    if seen is not None and (rep is not None or pres is not None
+                             or freq is not None):
+        lf = apply_penalties(lf, seen, 1.0 if rep is None else rep,
+                             0.0 if pres is None else pres,
+                             0.0 if freq is None else freq)
+    uf = u.reshape(-1)
+    tok = torch.tensor(
+        [_sample_row(lf[b], float(temp[b]), int(top_k[b]), float(top_p[b]),
+                     float(min_p[b]), float(uf[b])) for b in range(B)],
+        dtype=torch.int64, device=logits.device)
+    if seen is not None:
+        count_tokens(seen, tok)
+    return tok

@@ -22,8 +22,9 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from ..core.sampler import DecodingConfig, Sampler
+from ..core.sampler import DecodingConfig, Sampler, new_seen_table
 from ..models import KVCache, ModelConfig, get_ring_model
+from ..ops.reference import SEEN_PROMPT_BIT
 from .comm import Ring
 
 log = logging.getLogger("dnet")
@@ -132,6 +133,9 @@ class RingExecutor:
         self.kvs = [self.model.make_kv_cache(mb_size, smax)
                     for _ in range(mb_count)]
         self.sampler = Sampler(decoding or DecodingConfig())
+        # per-microbatch token history [mb_size, V]; exists only while the
+        # decoding config has a non-neutral penalty (set_decoding)
+        self.seen = None
         H = cfg.hidden_size
         # static buffers (recv targets / graph inputs)
         self.hbuf = [torch.zeros(mb_size, H, dtype=torch.bfloat16,
@@ -280,7 +284,9 @@ class RingExecutor:
     def prefill(self, tokens: torch.Tensor,
                 chunk: int = 0) -> torch.Tensor | None:
         """tokens: [mb_count, mb_size, T] int64 (significant on rank 0; other
-        ranks use it for shape only). Fills KV, samples the first token per
+        ranks use it for shape only, except that with a penalised decoding
+        config the sampling rank marks the prompt in ``seen`` and needs the
+        real tokens too). Fills KV, samples the first token per
         sequence. Returns first-token tensor [mb_count, mb_size] on rank 0
         (and on the last rank), else None.
 
@@ -321,7 +327,14 @@ class RingExecutor:
                                                     src=self.token_src))
             else:
                 logits = self.model.normalize_project(h[:, -1].contiguous())
-                tok, logprob, tops = self.sampler.sample(logits.float())
+                if self.seen is not None:
+                    # penalties: every rank that samples needs the real
+                    # prompt tokens, not just their shape
+                    self.seen[mb].zero_()
+                    self.seen[mb].scatter_(1, tokens[mb].to(self.device),
+                                           SEEN_PROMPT_BIT)
+                tok, logprob, tops = self.sampler.sample(logits.float(),
+                                                         self._seen(mb))
                 self.last_logprob, self.last_tops = logprob, tops
                 first_tokens[mb] = tok
                 if not self.is_first:
@@ -405,7 +418,8 @@ class RingExecutor:
                         if not (self.is_last and r == last_r):
                             send_h(mb)
                 if self.is_last:
-                    tok, _, _ = self.sampler.sample(self.logits_buf[mb].float())
+                    tok, _, _ = self.sampler.sample(
+                        self.logits_buf[mb].float(), self._seen(mb))
                     if self.stages > 1:
                         self.ring.send(tok, dst=self.token_dst)
                     else:
@@ -497,6 +511,15 @@ class RingExecutor:
             g = torch.Generator(device=self.device)
             g.manual_seed(int(seed))
         self.sampler = Sampler(cfg, generator=g)
+        if not cfg.has_penalty:
+            self.seen = None
+        elif self.seen is None:
+            self.seen = [new_seen_table(self.mb_size, self.cfg.vocab_size,
+                                        self.device)
+                         for _ in range(self.mb_count)]
+
+    def _seen(self, mb: int):
+        return self.seen[mb] if self.seen is not None else None
 
     def decode_stream(self, max_tokens: int, stop_ids=(), on_token=None,
                       mb: int = 0, should_stop=None):
@@ -540,7 +563,7 @@ class RingExecutor:
                         self._send_hidden(mb)
             if self.is_last:
                 tok, logprob, tops = self.sampler.sample(
-                    self.logits_buf[mb].float())
+                    self.logits_buf[mb].float(), self._seen(mb))
                 self.last_logprob, self.last_tops = logprob, tops
                 self.tokbuf[mb].copy_(tok)
             if self.world > 1:

@@ -193,7 +193,8 @@ class ShardRuntime:
         self.slots = [None] * req.max_batch if req.max_batch > 1 else None
         if self.slots is not None:
             from ..core.sampler import RowSampler
-            self._row_sampler = RowSampler(req.max_batch, device=ex.device)
+            self._row_sampler = RowSampler(req.max_batch, device=ex.device,
+                                           vocab=ex.cfg.vocab_size)
             # device-resident park masks (updated only on slot-state
             # CHANGES: building a park index tensor per tick was a
             # synchronous H2D that serialized the host against the
@@ -413,7 +414,10 @@ class ShardRuntime:
                                 p.get("temperature", 0.0), p.get("top_p", 1.0),
                                 p.get("top_k", 0), p.get("min_p", 0.0),
                                 int(p.get("logprobs", False)),
-                                int(p.get("top_logprobs", 0)), len(nonce_ids))
+                                int(p.get("top_logprobs", 0)), len(nonce_ids),
+                                p.get("repetition_penalty", 1.0),
+                                p.get("presence_penalty", 0.0),
+                                p.get("frequency_penalty", 0.0))
             import torch.distributed as dist
             payload = torch.cat([
                 tokens.flatten().to(self._comm_device()),
@@ -429,7 +433,8 @@ class ShardRuntime:
         n_nonce = int(cmd[10])
         p = {"temperature": cmd[4], "top_p": cmd[5], "top_k": int(cmd[6]),
              "min_p": cmd[7], "logprobs": bool(cmd[8]),
-             "top_logprobs": int(cmd[9])}
+             "top_logprobs": int(cmd[9]), "repetition_penalty": cmd[11],
+             "presence_penalty": cmd[12], "frequency_penalty": cmd[13]}
         payload = torch.zeros(T + n_stop + n_nonce, dtype=torch.int64,
                               device=self._comm_device())
         dist.broadcast(payload, src=0)
@@ -450,7 +455,10 @@ class ShardRuntime:
             temperature=p.get("temperature", 0.0), top_p=p.get("top_p", 1.0),
             top_k=int(p.get("top_k", 0)), min_p=p.get("min_p", 0.0),
             logprobs=bool(p.get("logprobs", False)),
-            top_logprobs=int(p.get("top_logprobs", 0))),
+            top_logprobs=int(p.get("top_logprobs", 0)),
+            repetition_penalty=float(p.get("repetition_penalty", 1.0)),
+            presence_penalty=float(p.get("presence_penalty", 0.0)),
+            frequency_penalty=float(p.get("frequency_penalty", 0.0))),
             seed=p.get("seed"))
         # pad the single sequence to the executor's batch width
         B = ex.mb_size
@@ -602,7 +610,10 @@ class ShardRuntime:
             temperature=p.get("temperature", 0.0), top_p=p.get("top_p", 1.0),
             top_k=int(p.get("top_k", 0)), min_p=p.get("min_p", 0.0),
             logprobs=bool(p.get("logprobs", False)),
-            top_logprobs=int(p.get("top_logprobs", 0)))
+            top_logprobs=int(p.get("top_logprobs", 0)),
+            repetition_penalty=float(p.get("repetition_penalty", 1.0)),
+            presence_penalty=float(p.get("presence_penalty", 0.0)),
+            frequency_penalty=float(p.get("frequency_penalty", 0.0)))
         stop_ids = list(frame.get("stop_ids", []))
         max_tokens = int(frame.get("max_tokens", 128))
         nonce = frame.get("nonce", "")
@@ -616,7 +627,8 @@ class ShardRuntime:
                                 cfg.min_p,
                                 -1.0 if seed is None else int(seed),
                                 1.0 if cfg.logprobs else 0.0,
-                                cfg.top_logprobs)
+                                cfg.top_logprobs, cfg.repetition_penalty,
+                                cfg.presence_penalty, cfg.frequency_penalty)
             payload = torch.cat([
                 tokens.flatten().to(self._comm_device()),
                 torch.tensor(stop_ids + nonce_ids, dtype=torch.int64,
@@ -632,7 +644,10 @@ class ShardRuntime:
         cfg = DecodingConfig(temperature=cmd[6], top_p=cmd[7],
                              top_k=int(cmd[8]), min_p=cmd[9],
                              logprobs=bool(cmd[11]),
-                             top_logprobs=int(cmd[12]))
+                             top_logprobs=int(cmd[12]),
+                             repetition_penalty=cmd[13],
+                             presence_penalty=cmd[14],
+                             frequency_penalty=cmd[15])
         seed = None if cmd[10] < 0 else int(cmd[10])
         payload = torch.zeros(T + n_stop + n_nonce, dtype=torch.int64,
                               device=self._comm_device())
@@ -653,6 +668,8 @@ class ShardRuntime:
         max_tokens = max(1, min(max_tokens,
                                 ex.smax - int(tokens.shape[-1])))
         gen = self._row_sampler.set_row(si, cfg, seed)
+        # the whole prompt is known here, also for a chunked prefill
+        self._row_sampler.note_prompt(si, tokens)
         chunk = int(os.environ.get("DNET_PREFILL_CHUNK", "2048"))
         if ex.world == 1 and int(tokens.shape[-1]) > chunk:
             # long prompt: admit in "prefill" state — the tick loop feeds
@@ -677,7 +694,8 @@ class ShardRuntime:
         lp0 = tops0 = None
         if ex.is_last:
             from ..core.sampler import Sampler
-            tok, lp, tops = Sampler(cfg, generator=gen).sample(logits.float())
+            tok, lp, tops = Sampler(cfg, generator=gen).sample(
+                logits.float(), self._row_sampler.seen_rows(si))
             t0_t[0] = int(tok[0])
             if lp is not None:
                 lp0 = float(lp[0])
@@ -687,6 +705,9 @@ class ShardRuntime:
             dist.broadcast(t0_t, src=(ex.stages - 1) * ex.tp)
         t0 = int(t0_t[0])
         ex.tokbuf[0][si] = t0
+        if not ex.is_last:
+            # the sampling rank counted it in Sampler.sample
+            self._row_sampler.note_token(si, t0)
         st = {"nonce": nonce, "produced": 1, "max_tokens": max_tokens,
               "stop_ids": set(stop_ids)}
         done = t0 in st["stop_ids"] or max_tokens <= 1
@@ -720,9 +741,13 @@ class ShardRuntime:
         kvslot.pos.fill_(T)
         logits = ex.model.normalize_project(h[:, -1].contiguous())
         from ..core.sampler import Sampler
+        # decode steps of the other slots sampled (and counted) this parked
+        # row's dummy logits while the prompt trickled in
+        self._row_sampler.reset_counts(si)
         tok, lp, tops = Sampler(st["cfg"],
                                 generator=self._row_sampler.gens[si]
-                                ).sample(logits.float())
+                                ).sample(logits.float(),
+                                         self._row_sampler.seen_rows(si))
         t0 = int(tok[0])
         lp0 = float(lp[0]) if lp is not None else None
         tops0 = tops[0] if tops else None
@@ -750,7 +775,7 @@ class ShardRuntime:
         rs = self._row_sampler
         ex.slot_step_compute()
         if ex.is_last:
-            toks_t = self._row_sampler.sample(ex.logits_buf[0].float())
+            toks_t = self._row_sampler.sample(ex.logits_buf[0])
             ex.tokbuf[0].copy_(toks_t)
         if ex.world > 1:
             import torch.distributed as dist
@@ -787,7 +812,7 @@ class ShardRuntime:
             self._launch_evs[0].record()
         ex.slot_step_compute()
         t0 = time.perf_counter()
-        toks_t = self._row_sampler.sample(ex.logits_buf[0].float())
+        toks_t = self._row_sampler.sample(ex.logits_buf[0])
         self._t_sample += time.perf_counter() - t0
         t0 = time.perf_counter()
         ex.tokbuf[0].copy_(toks_t)
