@@ -29,7 +29,7 @@ log = get_logger("api")
 def decoding_params(request: ChatRequestModel) -> dict:
     """The `params` dict of an infer request: every sampling control the
     shard runtime understands."""
-    return {
+    params = {
         "seed": request.seed,
         "temperature": request.temperature, "top_p": request.top_p,
         "top_k": request.top_k, "min_p": request.min_p,
@@ -38,6 +38,11 @@ def decoding_params(request: ChatRequestModel) -> dict:
         "frequency_penalty": request.frequency_penalty,
         "logprobs": request.logprobs,
         "top_logprobs": request.top_logprobs}
+    if request.logit_bias:
+        # pairs, not a map: msgpack rejects integer map keys on unpack
+        params["logit_bias"] = [[int(k), float(v)]
+                                for k, v in request.logit_bias.items()]
+    return params
 
 
 class InferenceManager:

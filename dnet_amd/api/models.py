@@ -8,7 +8,7 @@ import time
 import uuid
 from typing import Any, Optional
 
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, field_validator
 
 
 class ChatMessage(BaseModel):
@@ -32,12 +32,35 @@ class ChatRequestModel(BaseModel):
     repetition_penalty: float = Field(default=1.0, gt=0.0)
     presence_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
     frequency_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
+    # OpenAI logit_bias: token id (as a string key, below 2^31) -> bias in
+    # [-100, 100], at most 300 entries; anything else is a 422
+    logit_bias: Optional[dict[str, float]] = None
     stream: bool = False
     stop: Optional[list[str] | str] = None
     logprobs: bool = False
     top_logprobs: int = 0
     profile: bool = False            # emit metrics in the final chunk
     n: int = 1
+
+    @field_validator("logit_bias")
+    @classmethod
+    def _check_logit_bias(cls, v):
+        if v is None:
+            return v
+        if len(v) > 300:
+            raise ValueError("logit_bias: at most 300 entries")
+        for k, b in v.items():
+            # a token id: ASCII digits, below 2^31 (no vocabulary is larger,
+            # and the id must fit the int64 words the runtime broadcasts)
+            if not (k.isascii() and k.isdigit() and len(k) <= 10
+                    and int(k) < 2 ** 31):
+                raise ValueError(
+                    f"logit_bias: key {k!r} is not a token id "
+                    "(a non-negative integer below 2^31)")
+            if not -100.0 <= b <= 100.0:
+                raise ValueError(
+                    f"logit_bias: value {b!r} outside [-100, 100]")
+        return v
 
     @property
     def effective_max_tokens(self) -> int:

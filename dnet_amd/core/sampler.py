@@ -23,11 +23,17 @@ class DecodingConfig:
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # OpenAI `logit_bias`: token id -> additive bias on the raw logit
+    logit_bias: Optional[dict] = None
 
     @property
     def has_penalty(self) -> bool:
         return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
                 or self.frequency_penalty != 0.0)
+
+    @property
+    def has_bias(self) -> bool:
+        return bool(self.logit_bias)
 
 
 def new_seen_table(rows: int, vocab: int, device=None) -> torch.Tensor:
@@ -42,9 +48,28 @@ def mark_prompt(seen_row: torch.Tensor, tokens) -> None:
     seen_row[idx] |= _ops().ref.SEEN_PROMPT_BIT
 
 
+def fill_bias_row(row: torch.Tensor, logit_bias) -> None:
+    """Zero one [V] f32 row of a bias table and scatter a request's
+    `logit_bias` (id -> value) into it. Ids outside [0, V) are dropped and
+    never written; of two entries for one id the last wins."""
+    V = row.shape[0]
+    row.zero_()
+    ent = {int(k): float(v) for k, v in dict(logit_bias or {}).items()
+           if 0 <= int(k) < V}
+    if ent:
+        row[torch.tensor(list(ent), dtype=torch.long, device=row.device)] = \
+            torch.tensor(list(ent.values()), dtype=torch.float32,
+                         device=row.device)
+
+
 def _ops():
     from .. import ops
     return ops
+
+
+def _fused_on() -> bool:
+    from ..config import get_settings
+    return bool(get_settings().sampling.fused_sampler)
 
 
 class Sampler:
@@ -53,14 +78,19 @@ class Sampler:
         self.cfg = cfg or DecodingConfig()
         self.generator = generator
 
-    def sample(self, logits: torch.Tensor, seen: torch.Tensor | None = None):
+    def sample(self, logits: torch.Tensor, seen: torch.Tensor | None = None,
+               bias: torch.Tensor | None = None):
         """logits [B, V] -> (tokens [B] int64, logprob [B] or None,
-        top_logprobs list or None). With a `seen` table [B, V] the
-        config's penalties shape the choice (logprobs stay on the raw
-        logits) and the returned tokens are counted in it."""
+        top_logprobs list or None). A `bias` row [1, V] or table [B, V]
+        (f32, the request's logit_bias) is added to the raw logits first;
+        with a `seen` table [B, V] the config's penalties then shape the
+        choice and the returned tokens are counted in it. Logprobs stay on
+        the raw logits."""
         c = self.cfg
         lf = logits.float()
-        raw = lf
+        raw = logits if logits.dtype == torch.bfloat16 else lf
+        if bias is not None:
+            lf = _ops().apply_logit_bias(lf, bias.expand(lf.shape[0], -1))
         if seen is not None and c.has_penalty:
             lf = _ops().apply_penalties(lf, seen, c.repetition_penalty,
                                         c.presence_penalty,
@@ -104,10 +134,24 @@ class Sampler:
         return tok
 
     def _logprobs(self, raw, tok):
-        """Logprobs of the raw (unpenalised) f32 logits."""
+        """Logprobs of the raw (unbiased, unpenalised) logits: one launch
+        of the HIP logprob kernel on GPU logits, torch on f32 otherwise."""
         c = self.cfg
         if not c.logprobs:
             return tok, None, None
+        if raw.is_cuda and _fused_on():
+            B = raw.shape[0]
+            K = min(int(c.top_logprobs or 0), 20)
+            chosen, tv, ti = _ops().logprobs_rows(
+                raw, tok, torch.full((B,), K, dtype=torch.int32,
+                                     device=raw.device), K)
+            tops = None
+            if K:
+                tv, ti = tv.tolist(), ti.tolist()
+                tops = [{i: v for v, i in zip(tv[b], ti[b]) if i >= 0}
+                        for b in range(B)]
+            return tok, chosen, tops
+        raw = raw.float()
         logp = raw - torch.logsumexp(raw, dim=-1, keepdim=True)
         chosen = logp.gather(-1, tok.unsqueeze(-1)).squeeze(-1)
         tops = None
@@ -141,6 +185,11 @@ class RowSampler:
         self.freq = torch.zeros(batch, device=device)
         self._pen_py = [False] * batch
         self.seen: Optional[torch.Tensor] = None
+        # logit_bias: a dense [batch, V] f32 table, allocated when the
+        # first biased row is set, and a per-row on/off flag
+        self.bias: Optional[torch.Tensor] = None
+        self.bias_on = torch.zeros(batch, dtype=torch.bool, device=device)
+        self._bias_py = [False] * batch
         self._u0 = None            # zeros: uniforms of an all-greedy batch
         self.temp = torch.zeros(batch, device=device)
         self.top_p = torch.ones(batch, device=device)
@@ -157,6 +206,9 @@ class RowSampler:
         # them, and the emitter picks per row
         self.want_lp: list = [False] * batch
         self.n_top: list = [0] * batch
+        # the same per row for the HIP logprob kernel: -1 = row skipped
+        self._ntop_dev = torch.full((batch,), -1, dtype=torch.int32,
+                                    device=device)
         self.last_logp = None    # [B] device, chosen-token logprob
         self.last_topv = None    # [B, K] device
         self.last_topi = None
@@ -177,6 +229,16 @@ class RowSampler:
                                        self.device)
         if self.seen is not None:
             self.seen[i].zero_()
+        if cfg.has_bias:
+            if self.bias is None:
+                if self.vocab is None:
+                    raise ValueError("logit_bias needs RowSampler(vocab=...)")
+                self.bias = torch.zeros(self.batch, int(self.vocab),
+                                        dtype=torch.float32,
+                                        device=self.device)
+            fill_bias_row(self.bias[i], cfg.logit_bias)
+        self.bias_on[i] = cfg.has_bias
+        self._bias_py[i] = cfg.has_bias
         self.temp[i] = cfg.temperature
         self.top_p[i] = cfg.top_p
         self.top_k[i] = cfg.top_k
@@ -185,6 +247,7 @@ class RowSampler:
             self._has_min_p = True
         self.want_lp[i] = bool(cfg.logprobs)
         self.n_top[i] = int(cfg.top_logprobs or 0)
+        self._ntop_dev[i] = min(self.n_top[i], 20) if cfg.logprobs else -1
         self._temp_py[i] = float(cfg.temperature)
         self._filt_py[i] = bool(cfg.top_k or cfg.top_p < 1.0 or cfg.min_p)
         g = None
@@ -205,10 +268,13 @@ class RowSampler:
         self.pres[i] = 0.0
         self.freq[i] = 0.0
         self._pen_py[i] = False
+        self.bias_on[i] = False
+        self._bias_py[i] = False
         self._temp_py[i] = 0.0
         self._filt_py[i] = False
         self.want_lp[i] = False
         self.n_top[i] = 0
+        self._ntop_dev[i] = -1
         self.gens[i] = None
 
     def note_prompt(self, i: int, tokens) -> None:
@@ -221,6 +287,13 @@ class RowSampler:
         or None when the row carries no penalty."""
         if self.seen is not None and self._pen_py[i]:
             return self.seen[i:i + 1]
+        return None
+
+    def bias_rows(self, i: int):
+        """Row i of the bias table as a [1, V] row for ``Sampler``, or None
+        when the row carries no logit_bias."""
+        if self.bias is not None and self._bias_py[i]:
+            return self.bias[i:i + 1]
         return None
 
     def reset_counts(self, i: int) -> None:
@@ -248,7 +321,22 @@ class RowSampler:
         return u
 
     def _logprobs_for(self, lf, tok):
+        """Logprobs of the raw logits for the rows that want them: GPU
+        logits (bf16 or f32 as they come) take one launch of the HIP
+        logprob kernel, which skips the other rows; the torch path works
+        on f32 over the whole batch."""
         B = lf.shape[0]
+        if lf.is_cuda and self.fused:
+            if any(self.want_lp[:B]):
+                kmax = min(max(self.n_top[:B]), 20)
+                self.last_logp, tv, ti = _ops().logprobs_rows(
+                    lf, tok, self._ntop_dev, kmax)
+                self.last_topv, self.last_topi = (tv, ti) if kmax else \
+                    (None, None)
+            else:
+                self.last_logp = self.last_topv = self.last_topi = None
+            return
+        lf = lf.float()
         if any(self.want_lp[:B]):
             logp = lf - torch.logsumexp(lf, dim=-1, keepdim=True)
             self.last_logp = logp.gather(-1, tok.unsqueeze(-1)).squeeze(-1)
@@ -264,21 +352,27 @@ class RowSampler:
     def sample(self, logits: torch.Tensor) -> torch.Tensor:
         B, V = logits.shape
         pen = any(self._pen_py[:B])
+        biased = any(self._bias_py[:B])
         sampled = any(t > 0 for t in self._temp_py[:B])
-        if logits.is_cuda and self.fused and (pen or sampled):
-            # one launch over the bf16 logits: penalties, temperature,
-            # filters and the draw, sort-free
-            tok = _ops().sample_rows(
-                logits, self.temp, self.top_k, self.top_p, self.min_p,
-                self._uniforms(B, logits.device) if sampled else self._zeros(),
-                self.rep if pen else None, self.pres if pen else None,
-                self.freq if pen else None, self.seen if pen else None)
-            if any(self.want_lp[:B]):
-                self._logprobs_for(logits.float(), tok)
+        if logits.is_cuda and self.fused:
+            if pen or sampled or biased:
+                # one launch over the bf16 logits: bias, penalties,
+                # temperature, filters and the draw, sort-free
+                tok = _ops().sample_rows(
+                    logits, self.temp, self.top_k, self.top_p, self.min_p,
+                    self._uniforms(B, logits.device) if sampled
+                    else self._zeros(),
+                    self.rep if pen else None, self.pres if pen else None,
+                    self.freq if pen else None, self.seen if pen else None,
+                    bias=self.bias if biased else None,
+                    bias_on=self.bias_on if biased else None)
             else:
-                self.last_logp = self.last_topv = self.last_topi = None
+                tok = logits.float().argmax(dim=-1)   # all-greedy fast path
+            self._logprobs_for(logits, tok)
             return tok
         raw = lf = logits.float()
+        if biased:
+            lf = _ops().apply_logit_bias(lf, self.bias, self.bias_on)
         if pen:
             lf = _ops().apply_penalties(lf, self.seen, self.rep, self.pres,
                                         self.freq)

@@ -409,17 +409,23 @@ mxfp4_dequant = ref.mxfp4_dequant
 quantize_mxfp4 = ref.quantize_mxfp4
 apply_penalties = ref.apply_penalties
 count_tokens = ref.count_tokens
+apply_logit_bias = ref.apply_logit_bias
 
 
 def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
                 top_k: torch.Tensor, top_p: torch.Tensor,
                 min_p: torch.Tensor, u: torch.Tensor, rep=None, pres=None,
                 freq=None, seen: torch.Tensor | None = None,
-                out: torch.Tensor | None = None) -> torch.Tensor:
+                out: torch.Tensor | None = None,
+                bias: torch.Tensor | None = None,
+                bias_on: torch.Tensor | None = None) -> torch.Tensor:
     """Fused per-row sampler: logits [B, V] (bf16 or f32, row stride >= V)
     -> tokens [B] int64. Per-row temp / top_k / top_p / min_p and a uniform
     u in [0, 1); optional rep / pres / freq penalties over the int32 `seen`
-    table [>= B, V], whose count for the returned token is incremented. The
+    table [>= B, V], whose count for the returned token is incremented;
+    optional f32 `bias` table [>= B, V] (dense rows, any stride >= V),
+    added to the raw logit before the penalties on the rows whose
+    `bias_on` flag (bool [>= B]) is set, on every row without flags. The
     parameter tensors may be longer than B. One launch on the current
     stream, no host sync; semantics in ``reference.sample_rows``."""
     if logits.is_cuda:
@@ -429,10 +435,35 @@ def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
         if top_k.dtype != torch.int64:
             top_k = top_k.to(torch.int64)
         _native().sample_rows(logits, temp, top_k, top_p, min_p, rep, pres,
-                              freq, seen, u.reshape(-1), out)
+                              freq, seen, u.reshape(-1), out, bias,
+                              bias_on if bias is not None else None)
         return out[:B]
     return ref.sample_rows(logits, temp, top_k, top_p, min_p, u, rep, pres,
-                           freq, seen)
+                           freq, seen, bias, bias_on)
+
+
+def logprobs_rows(logits: torch.Tensor, tok: torch.Tensor,
+                  n_top: torch.Tensor, K: int, logp=None, topv=None,
+                  topi=None):
+    """Chosen-token and ordered top-K logprobs of raw logits [B, V] (bf16
+    or f32, row stride >= V) -> (logp [B] f32, topv [B, K] f32, topi [B, K]
+    int64), 0 <= K <= 20. `tok` [B] int64; `n_top` [B] int32 on the logits'
+    device: -1 skips the row (its entries of the given outputs stay
+    untouched), 0..20 is the number of top entries wanted; the rest up to K
+    is (-1, NaN). One launch on the current stream, no sort, no host sync,
+    bit-reproducible; semantics in ``reference.logprobs_rows``."""
+    if logits.is_cuda:
+        B = logits.shape[0]
+        dev = logits.device
+        if logp is None:
+            logp = torch.empty(B, dtype=torch.float32, device=dev)
+        if topv is None:
+            topv = torch.empty(B, K, dtype=torch.float32, device=dev)
+        if topi is None:
+            topi = torch.empty(B, K, dtype=torch.int64, device=dev)
+        _native().logprobs_rows(logits, tok, n_top, logp, topv, topi)
+        return logp, topv, topi
+    return ref.logprobs_rows(logits, tok, n_top, K, logp, topv, topi)
 
 
 def dequant_mxfp4(w: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:

@@ -71,7 +71,11 @@ void sample_rows(torch::Tensor logits, torch::Tensor temp, torch::Tensor top_k,
                  c10::optional<torch::Tensor> pres,
                  c10::optional<torch::Tensor> freq,
                  c10::optional<torch::Tensor> seen, torch::Tensor u,
-                 torch::Tensor out_tok);
+                 torch::Tensor out_tok, c10::optional<torch::Tensor> bias,
+                 c10::optional<torch::Tensor> bias_on);
+void logprobs_rows(torch::Tensor logits, torch::Tensor tok,
+                   torch::Tensor n_top, torch::Tensor logp, torch::Tensor topv,
+                   torch::Tensor topi);
 }  // namespace dnet
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -129,5 +133,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused per-row penalties + temperature + top-k/top-p/min-p + draw",
         py::arg("logits"), py::arg("temp"), py::arg("top_k"), py::arg("top_p"),
         py::arg("min_p"), py::arg("rep"), py::arg("pres"), py::arg("freq"),
-        py::arg("seen"), py::arg("u"), py::arg("out_tok"));
+        py::arg("seen"), py::arg("u"), py::arg("out_tok"),
+        py::arg("bias") = c10::nullopt, py::arg("bias_on") = c10::nullopt);
+  m.def("logprobs_rows", &dnet::logprobs_rows,
+        "chosen-token and ordered top-K logprobs per row, sort-free");
 }

@@ -24,178 +24,31 @@
 // v_exp_f32 on (l - l_max) * (log2(e) / temp)); the select passes compare
 // keys and weigh only tokens under the current prefix.
 //
+// A row whose logit-bias flag is on adds its row of the dense f32 bias table
+// to the raw logit (one f32 add) before the penalties, in every pass; a row
+// whose flag is off never reads the table. The kernel is compiled twice: a
+// call without a table launches the instance that has no bias code at all.
+//
 // Every mass is carried as an unsigned 64-bit fixed-point number with step
 // 2^-40 (e_i <= 1, so a row of 2^18 tokens sums below 2^58). Integer sums
 // are exact in any order: LDS histogram atomics, block reductions and the
 // draw are bit-reproducible, and the top-p decision `mass_above < p*T` is
 // made on the same integers the draw uses.
-#include "common.h"
-
-#include <climits>
-#include <cmath>
+#include "sample_common.h"
 
 namespace dnet {
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kBins = 2048;          // 11-bit radix digit
-constexpr float kFxScale = 0x1p40f;  // fixed-point step 2^-40
-constexpr int kCountMask = 0x3FFFFFFF;
-constexpr int kPromptBit = 0x40000000;
-
-using u64 = unsigned long long;
-
-template <typename T> struct VecOf;
-template <> struct VecOf<short> { static constexpr int n = 8; };  // bf16 bits
-template <> struct VecOf<float> { static constexpr int n = 4; };
-
-struct Row {
-  const void* l;    // first element of the row
-  const int* seen;  // row of the seen table, or nullptr when no penalty acts
-  int V;
-  int off;          // elements between the previous 16-B boundary and l
-  bool seen_vec;    // seen row shares the 16-B phase of the logits row
-  float rep, pres, freq;
-};
-
-__device__ __forceinline__ float penalise(float l, const int w, const Row& r) {
-  const int c = w & kCountMask;
-  if ((c > 0 || (w & kPromptBit)) && r.rep != 1.f)
-    l = l > 0.f ? __fdiv_rn(l, r.rep) : __fmul_rn(l, r.rep);
-  l = __fsub_rn(l, __fmul_rn(r.freq, (float)c));
-  if (c > 0) l = __fsub_rn(l, r.pres);
-  return l;
-}
-
-// Slot s holds elements [s*N - off, s*N - off + N). Elements outside
-// [0, V) come back as NaN, which every pass ignores.
-template <typename T>
-__device__ __forceinline__ void load_slot(const Row& r, const int s,
-                                          float (&v)[VecOf<T>::n]) {
-  constexpr int N = VecOf<T>::n;
-  const int e0 = s * N - r.off;
-  int w[N];
-  if (e0 >= 0 && e0 + N <= r.V) {
-    const T* p = reinterpret_cast<const T*>(r.l) + e0;
-    if constexpr (N == 8) {
-      const short8 raw = *reinterpret_cast<const short8*>(p);
-#pragma unroll
-      for (int j = 0; j < N; ++j) v[j] = bits2f(raw.x[j]);
-    } else {
-      const float4 raw = *reinterpret_cast<const float4*>(p);
-      v[0] = raw.x; v[1] = raw.y; v[2] = raw.z; v[3] = raw.w;
-    }
-    if (r.seen) {
-      const int* sp = r.seen + e0;
-      if (r.seen_vec) {
-#pragma unroll
-        for (int j = 0; j < N; j += 4) {
-          const int4 q = *reinterpret_cast<const int4*>(sp + j);
-          w[j] = q.x; w[j + 1] = q.y; w[j + 2] = q.z; w[j + 3] = q.w;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < N; ++j) w[j] = sp[j];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const int idx = e0 + j;
-      const bool ok = idx >= 0 && idx < r.V;
-      float f = NAN;
-      if (ok) {
-        if constexpr (N == 8)
-          f = bits2f(reinterpret_cast<const short*>(r.l)[idx]);
-        else
-          f = reinterpret_cast<const float*>(r.l)[idx];
-      }
-      v[j] = f;
-      w[j] = (ok && r.seen) ? r.seen[idx] : 0;
-    }
-  }
-  if (r.seen) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) v[j] = penalise(v[j], w[j], r);
-  }
-}
-
-// f(idx, penalised logit) over this lane's share of slots [s0, s1).
-template <typename T, typename F>
-__device__ __forceinline__ void sweep(const Row& r, const int s0, const int s1,
-                                      const int lane, F&& f) {
-  constexpr int N = VecOf<T>::n;
-  for (int s = s0 + lane; s < s1; s += kWave) {
-    float v[N];
-    load_slot<T>(r, s, v);
-    const int e0 = s * N - r.off;
-#pragma unroll
-    for (int j = 0; j < N; ++j) f(e0 + j, v[j]);
-  }
-}
-
-// Order-preserving key: a > b  <=>  fkey(a) > fkey(b) for non-NaN floats,
-// and a == b <=> equal keys (-0 is folded onto +0 first).
-__device__ __forceinline__ unsigned fkey(const float a) {
-  const unsigned u = __float_as_uint(a + 0.f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// distance to the max (<= 0), the exponent before scaling
-__device__ __forceinline__ float dist(const float l, const float lmax) {
-  return __fsub_rn(l, lmax) + 0.f;
-}
-// e = exp(d / temp) as 2^(d * c), c = log2(e) / temp held as hi + lo so
-// that the product rounds once, then the 1-ulp v_exp_f32
-struct Scale { float hi, lo; };
-// Below 2^-160 (a -inf logit included) the weight is exactly 0: it is 0 in
-// fixed point anyway, and d * c.lo must not meet an overflowed d * c.hi.
-__device__ __forceinline__ float weight(const float d, const Scale c) {
-  if (!(__fmul_rn(d, c.hi) >= -160.f)) return 0.f;
-  return __builtin_amdgcn_exp2f(__fmaf_rn(d, c.hi, __fmul_rn(d, c.lo)));
-}
-__device__ __forceinline__ u64 to_fx(const float e) {
-  return (u64)__fmul_rn(e, kFxScale);
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return __shfl(v, 0, 64);
-}
-
-__device__ __forceinline__ u64 wave_incl_scan_u64(u64 v, const int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const u64 o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-
-// Exclusive prefix sum of v over threadIdx.x. lds holds kWaves values.
-__device__ __forceinline__ u64 block_excl_scan_u64(const u64 v, u64* lds) {
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const u64 incl = wave_incl_scan_u64(v, lane);
-  __syncthreads();
-  if (lane == kWave - 1) lds[wid] = incl;
-  __syncthreads();
-  u64 base = 0;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) base += (i < wid) ? lds[i] : 0;
-  return base + incl - v;
-}
-
-template <typename T>
+template <typename T, bool kBias>
 __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
     const T* __restrict__ logits, const int64_t stride, const int V,
     const float* __restrict__ temp, const int64_t* __restrict__ top_k,
     const float* __restrict__ top_p, const float* __restrict__ min_p,
     const float* __restrict__ rep, const float* __restrict__ pres,
     const float* __restrict__ freq, int* __restrict__ seen,
-    const int64_t seen_stride, const float* __restrict__ u,
-    int64_t* __restrict__ out) {
+    const int64_t seen_stride, const float* __restrict__ bias,
+    const int64_t bias_stride, const unsigned char* __restrict__ bias_on,
+    const float* __restrict__ u, int64_t* __restrict__ out) {
   constexpr int N = VecOf<T>::n;
   __shared__ u64 s_mass[kBins];
   __shared__ unsigned s_cnt[kBins];
@@ -223,12 +76,14 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
   const bool pen = seen_row && (r.rep != 1.f || r.pres != 0.f || r.freq != 0.f);
   r.seen = pen ? seen_row : nullptr;
   r.seen_vec = (((uintptr_t)seen_row - 4 * (uintptr_t)r.off) & 15) == 0;
+  // a row whose flag is off never touches the bias table
+  r.bias = (kBias && bias && (!bias_on || bias_on[b]))
+               ? bias + (int64_t)b * bias_stride
+               : nullptr;
+  r.bias_vec = (((uintptr_t)r.bias - 4 * (uintptr_t)r.off) & 15) == 0;
 
-  // wave w owns slots [s0, s1): contiguous, a multiple of 64 long
-  const int nslots = (V + r.off + N - 1) / N;
-  const int spw = ((nslots + kWaves - 1) / kWaves + kWave - 1) / kWave * kWave;
-  const int s0 = min(wid * spw, nslots);
-  const int s1 = min(s0 + spw, nslots);
+  int s0, s1;
+  wave_range<T>(r, wid, s0, s1);
 
   // thread 0 publishes the token and counts it
   auto finish = [&](const int tok) {
@@ -244,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
   // ---- pass 1: max, argmax, first NaN ---------------------------------
   float bv = -INFINITY;
   int bi = INT_MAX, nan_i = INT_MAX;
-  sweep<T>(r, s0, s1, lane, [&](const int idx, const float x) {
+  sweep<T, kBias>(r, s0, s1, lane, [&](const int idx, const float x) {
     if (x > bv) { bv = x; bi = idx; }  // indices rise: ties keep the lowest
     if (x != x && idx >= 0 && idx < V) nan_i = min(nan_i, idx);
   });
@@ -295,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
   c.hi = (float)cd;
   c.lo = (float)(cd - (double)c.hi);
   u64 tsum = 0;
-  sweep<T>(r, s0, s1, lane, [&](const int, const float x) {
+  sweep<T, kBias>(r, s0, s1, lane, [&](const int, const float x) {
     if (x != x) return;
     const u64 q = to_fx(weight(dist(x, lmax), c));
     tsum += q;
@@ -328,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
         for (int i = tid; i < kBins; i += kThreads) { s_cnt[i] = 0; s_mass[i] = 0; }
         __syncthreads();
         const int up = shift + bits;  // bits already fixed sit above `up`
-        sweep<T>(r, s0, s1, lane, [&](const int, const float x) {
+        sweep<T, kBias>(r, s0, s1, lane, [&](const int, const float x) {
           if (x != x) return;
           const unsigned key = fkey(x);
           const unsigned d = (key >> shift) & (nb - 1);
@@ -380,7 +235,7 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
   // ---- pass 5: kept mass per wave, locate the wave ---------------------
   if (key_thr != 0u || on_mp) {  // else every token is kept: pass 2's totals
     u64 ksum = 0;
-    sweep<T>(r, s0, s1, lane,
+    sweep<T, kBias>(r, s0, s1, lane,
              [&](const int, const float x) { ksum += kept_fx(x); });
     ksum = wave_sum_u64(ksum);
     __syncthreads();  // pass 2's totals have been read
@@ -408,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(
     u64 sum = 0;
     if (s < s1) {
       float v[N];
-      load_slot<T>(r, s, v);
+      load_slot<T, kBias>(r, s, v);
 #pragma unroll
       for (int j = 0; j < N; ++j) { q[j] = kept_fx(v[j]); sum += q[j]; }
     } else {
@@ -444,7 +299,8 @@ void sample_rows(torch::Tensor logits, torch::Tensor temp, torch::Tensor top_k,
                  c10::optional<torch::Tensor> pres,
                  c10::optional<torch::Tensor> freq,
                  c10::optional<torch::Tensor> seen, torch::Tensor u,
-                 torch::Tensor out_tok) {
+                 torch::Tensor out_tok, c10::optional<torch::Tensor> bias,
+                 c10::optional<torch::Tensor> bias_on) {
   DNET_CHECK(logits.is_cuda() && logits.dim() == 2, "logits: [B, V] on GPU");
   const int64_t B = logits.size(0), V = logits.size(1);
   DNET_CHECK(B >= 1 && V >= 1 && V < (1 << 30), "B >= 1, 1 <= V < 2^30");
@@ -480,22 +336,44 @@ void sample_rows(torch::Tensor logits, torch::Tensor temp, torch::Tensor top_k,
     sp = (int*)seen->data_ptr();
     sstride = seen->stride(0);
   }
+  const float* bp = nullptr;
+  const unsigned char* bop = nullptr;
+  int64_t bstride = 0;
+  if (bias.has_value()) {
+    DNET_CHECK(bias->is_cuda() && bias->dtype() == torch::kFloat32 &&
+                   bias->dim() == 2 && bias->size(0) >= B &&
+                   bias->size(1) == V && bias->stride(1) == 1 &&
+                   bias->stride(0) >= V,
+               "bias: f32 [>= B, V] with dense rows on GPU");
+    bp = (const float*)bias->data_ptr();
+    bstride = bias->stride(0);
+    if (bias_on.has_value()) {
+      DNET_CHECK(bias_on->is_cuda() &&
+                     (bias_on->dtype() == torch::kBool ||
+                      bias_on->dtype() == torch::kUInt8) &&
+                     bias_on->is_contiguous() && bias_on->numel() >= B,
+                 "bias_on: contiguous bool with >= B elements on GPU");
+      bop = (const unsigned char*)bias_on->data_ptr();
+    }
+  }
   auto stream = current_stream();
-  if (logits.dtype() == torch::kBFloat16) {
-    hipLaunchKernelGGL(sample_rows_kernel<short>, dim3((unsigned)B),
-                       dim3(kThreads), 0, stream,
-                       (const short*)logits.data_ptr(), logits.stride(0),
-                       (int)V, tp, (const int64_t*)top_k.data_ptr(), pp, mp,
-                       rp, prp, fp, sp, sstride, up,
+  // a call without a table launches the kernel compiled without the bias
+  auto launch = [&](auto kernel, auto* lp) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kThreads), 0, stream,
+                       lp, logits.stride(0), (int)V, tp,
+                       (const int64_t*)top_k.data_ptr(), pp, mp, rp, prp, fp,
+                       sp, sstride, bp, bstride, bop, up,
                        (int64_t*)out_tok.data_ptr());
+  };
+  if (logits.dtype() == torch::kBFloat16) {
+    const short* lp = (const short*)logits.data_ptr();
+    if (bp) launch(sample_rows_kernel<short, true>, lp);
+    else launch(sample_rows_kernel<short, false>, lp);
   } else {
     DNET_CHECK(logits.dtype() == torch::kFloat32, "logits: bf16 or f32");
-    hipLaunchKernelGGL(sample_rows_kernel<float>, dim3((unsigned)B),
-                       dim3(kThreads), 0, stream,
-                       (const float*)logits.data_ptr(), logits.stride(0),
-                       (int)V, tp, (const int64_t*)top_k.data_ptr(), pp, mp,
-                       rp, prp, fp, sp, sstride, up,
-                       (int64_t*)out_tok.data_ptr());
+    const float* lp = (const float*)logits.data_ptr();
+    if (bp) launch(sample_rows_kernel<float, true>, lp);
+    else launch(sample_rows_kernel<float, false>, lp);
   }
   DNET_CHECK_HIP(hipGetLastError());
 }

@@ -513,6 +513,20 @@ def count_tokens(seen: torch.Tensor, tok: torch.Tensor) -> None:
                                   w, w + 1)
 
 
+def apply_logit_bias(lf: torch.Tensor, bias: torch.Tensor,
+                     bias_on=None) -> torch.Tensor:
+    """OpenAI `logit_bias` on raw f32 logits [B, V]: l' = fl32(l + bias[b])
+    on the rows whose flag is on (all rows when `bias_on` is None), before
+    any penalty. `bias` [>= B, V] f32; rows with the flag off are not
+    read into the result, whatever they hold. Works on any device."""
+    B = lf.shape[0]
+    lb = lf + bias[:B].to(lf.device, torch.float32)
+    if bias_on is None:
+        return lb
+    on = bias_on[:B].to(lf.device).bool().unsqueeze(-1)
+    return torch.where(on, lb, lf)
+
+
 def _sample_row(l: torch.Tensor, temp: float, top_k: int, top_p: float,
                 min_p: float, u: float) -> int:
     """One row of penalised f32 logits -> token (see sample_rows)."""
@@ -554,9 +568,15 @@ def _sample_row(l: torch.Tensor, temp: float, top_k: int, top_p: float,
 def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
                 top_k: torch.Tensor, top_p: torch.Tensor,
                 min_p: torch.Tensor, u: torch.Tensor, rep=None, pres=None,
-                freq=None, seen: torch.Tensor | None = None) -> torch.Tensor:
+                freq=None, seen: torch.Tensor | None = None,
+                bias: torch.Tensor | None = None,
+                bias_on=None) -> torch.Tensor:
     """Per-row sampling, the contract of the fused HIP sampler.
 
+    A row whose `bias_on` flag is set (every row when only `bias` is
+    given) first adds its row of the f32 `bias` table [>= B, V] to the raw
+    logit, l' = fl32(l + bias): the penalties act on l' and see its sign,
+    and a NaN l' is ignored like any NaN logit.
     Penalties act on the raw f32 logit (rows of `seen`), `temp <= 0` rows
     take the argmax (lowest index on ties). Otherwise with
     x = l / temp, e = exp(x - max x), T = sum e, token i is kept iff
@@ -566,6 +586,8 @@ def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
     exceeds u * S. When `seen` is given the returned token is counted."""
     B = logits.shape[0]
     lf = logits.float()
+    if bias is not None:
+        lf = apply_logit_bias(lf, bias, bias_on)
     if seen is not None and (rep is not None or pres is not None
                              or freq is not None):
         lf = apply_penalties(lf, seen, 1.0 if rep is None else rep,
@@ -579,3 +601,52 @@ def sample_rows(logits: torch.Tensor, temp: torch.Tensor,
     if seen is not None:
         count_tokens(seen, tok)
     return tok
+
+
+def logprobs_rows(logits: torch.Tensor, tok: torch.Tensor,
+                  n_top: torch.Tensor, K: int, logp=None, topv=None,
+                  topi=None):
+    """Chosen-token and top-K logprobs of raw logits [B, V], the contract
+    of the HIP logprob kernel -> (logp [B] f32, topv [B, K] f32,
+    topi [B, K] int64).
+
+    NaN logits are absent. With m the largest non-NaN logit and
+    T = sum exp(l_i - m), logp(j) = (l_j - m) - ln T: -inf for a -inf
+    logit, NaN for a NaN logit, and NaN for every j when m = +inf or
+    nothing lies above -inf. `tok[b]` outside [0, V) gives NaN. The top
+    list is ordered by logit descending, then index ascending (a stable
+    sort of the exact input values, so ties are decided); entry
+    r < min(n_top[b], #non-NaN) is (index, logp(index)), every other entry
+    up to K is (-1, NaN). A row with n_top[b] < 0 is skipped: its entries
+    of the given output tensors are left as they are."""
+    B, V = logits.shape
+    dev = logits.device
+    if logp is None:
+        logp = torch.full((B,), float("nan"), device=dev)
+    if topv is None:
+        topv = torch.full((B, K), float("nan"), device=dev)
+    if topi is None:
+        topi = torch.full((B, K), -1, dtype=torch.int64, device=dev)
+    lf = logits.float()
+    for b in range(B):
+        nt = int(n_top[b])
+        if nt < 0:
+            continue
+        l = lf[b]
+        nan = torch.isnan(l)
+        lv = torch.where(nan, torch.full_like(l, float("-inf")), l)
+        m = lv.max()
+        d = l - m                          # NaN where it has to be
+        lp = d - torch.log(torch.exp(torch.where(nan, lv, d)).sum())
+        if not (m > float("-inf")) or m == float("inf") or bool(nan.all()):
+            lp = torch.full_like(l, float("nan"))
+        j = int(tok[b])
+        logp[b] = lp[j] if 0 <= j < V else float("nan")
+        order = torch.sort(lv, descending=True, stable=True).indices
+        order = order[~nan[order]]
+        n = min(nt, K, int(order.numel()))
+        topi[b, :n] = order[:n]
+        topv[b, :n] = lp[order[:n]]
+        topi[b, n:] = -1
+        topv[b, n:] = float("nan")
+    return logp, topv, topi

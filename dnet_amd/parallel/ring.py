@@ -22,7 +22,8 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from ..core.sampler import DecodingConfig, Sampler, new_seen_table
+from ..core.sampler import (DecodingConfig, Sampler, fill_bias_row,
+                            new_seen_table)
 from ..models import KVCache, ModelConfig, get_ring_model
 from ..ops.reference import SEEN_PROMPT_BIT
 from .comm import Ring
@@ -136,6 +137,7 @@ class RingExecutor:
         # per-microbatch token history [mb_size, V]; exists only while the
         # decoding config has a non-neutral penalty (set_decoding)
         self.seen = None
+        self.bias_row = None       # [1, V] f32 logit_bias (set_decoding)
         H = cfg.hidden_size
         # static buffers (recv targets / graph inputs)
         self.hbuf = [torch.zeros(mb_size, H, dtype=torch.bfloat16,
@@ -333,8 +335,8 @@ class RingExecutor:
                     self.seen[mb].zero_()
                     self.seen[mb].scatter_(1, tokens[mb].to(self.device),
                                            SEEN_PROMPT_BIT)
-                tok, logprob, tops = self.sampler.sample(logits.float(),
-                                                         self._seen(mb))
+                tok, logprob, tops = self.sampler.sample(
+                    logits, self._seen(mb), self.bias_row)
                 self.last_logprob, self.last_tops = logprob, tops
                 first_tokens[mb] = tok
                 if not self.is_first:
@@ -419,7 +421,8 @@ class RingExecutor:
                             send_h(mb)
                 if self.is_last:
                     tok, _, _ = self.sampler.sample(
-                        self.logits_buf[mb].float(), self._seen(mb))
+                        self.logits_buf[mb], self._seen(mb),
+                        self.bias_row)
                     if self.stages > 1:
                         self.ring.send(tok, dst=self.token_dst)
                     else:
@@ -511,6 +514,14 @@ class RingExecutor:
             g = torch.Generator(device=self.device)
             g.manual_seed(int(seed))
         self.sampler = Sampler(cfg, generator=g)
+        # logit_bias of the serial path: one [1, V] f32 row for every
+        # microbatch row (they all carry the same request)
+        self.bias_row = None
+        if cfg.has_bias:
+            self.bias_row = torch.zeros(1, self.cfg.vocab_size,
+                                        dtype=torch.float32,
+                                        device=self.device)
+            fill_bias_row(self.bias_row[0], cfg.logit_bias)
         if not cfg.has_penalty:
             self.seen = None
         elif self.seen is None:
@@ -563,7 +574,8 @@ class RingExecutor:
                         self._send_hidden(mb)
             if self.is_last:
                 tok, logprob, tops = self.sampler.sample(
-                    self.logits_buf[mb].float(), self._seen(mb))
+                    self.logits_buf[mb], self._seen(mb),
+                    self.bias_row)
                 self.last_logprob, self.last_tops = logprob, tops
                 self.tokbuf[mb].copy_(tok)
             if self.world > 1:

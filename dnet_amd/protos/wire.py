@@ -10,6 +10,9 @@ Frame types (the protocol contract):
   api -> shard0 : {"t": "infer", "nonce", "tokens": bytes(int32 LE),
                    "prompt_len", "max_tokens", "params": {...},
                    "stop_ids": [...], "callback": "host:port"}
+                  params carries the sampling controls; its "logit_bias" is
+                  a list of [token_id, bias] pairs (a list, not a map:
+                  integer map keys do not survive the msgpack round trip)
   api -> shard0 : {"t": "reset", "nonce"}
   api -> shard0 : {"t": "ping"} -> {"t": "pong"}
   last -> api   : {"t": "token", "nonce", "token_id", "ts_ms",

@@ -369,7 +369,31 @@ class ShardRuntime:
 
     # ---------- collective command plumbing ----------
 
-    _CMD_LEN = 16
+    _CMD_LEN = 17      # slot 16: number of logit_bias entries
+
+    def _bias_pairs(self, p: dict) -> list:
+        """params["logit_bias"] ([[id, bias], ...]) -> [(int, float), ...],
+        ids outside [0, vocab) dropped here, before anything is broadcast:
+        they would never be written into a bias row, and an id past 2^63
+        does not fit the int64 payload."""
+        V = int(self.executor.cfg.vocab_size)
+        return [(int(k), float(v)) for k, v in (p.get("logit_bias") or [])
+                if 0 <= int(k) < V]
+
+    @staticmethod
+    def _bias_payload(pairs) -> list:
+        """int64 words for the payload broadcast: the ids, then the
+        float64 bit patterns of the values, so every rank gets exactly the
+        bias rank 0 got."""
+        import struct
+        return [k for k, _ in pairs] + [
+            struct.unpack("<q", struct.pack("<d", v))[0] for _, v in pairs]
+
+    @staticmethod
+    def _bias_from_payload(words: list, n: int) -> dict:
+        import struct
+        return {int(k): struct.unpack("<d", struct.pack("<q", int(w)))[0]
+                for k, w in zip(words[:n], words[n:2 * n])}
 
     def _cmd_tensor(self, vals=()):
         t = torch.zeros(self._CMD_LEN, dtype=torch.float64,
@@ -409,7 +433,14 @@ class ShardRuntime:
         stop_ids = list(frame.get("stop_ids", []))
         nonce = frame.get("nonce", "")
         nonce_ids = list(nonce.encode("utf-8"))[:64]
+        pairs = self._bias_pairs(p)
         if ex.world > 1:
+            # built first: nothing may raise between the two broadcasts
+            payload = torch.cat([
+                tokens.flatten().to(self._comm_device()),
+                torch.tensor(stop_ids + nonce_ids
+                             + self._bias_payload(pairs), dtype=torch.int64,
+                             device=self._comm_device())])
             self._broadcast_cmd(CMD_INFER, T, max_tokens, len(stop_ids),
                                 p.get("temperature", 0.0), p.get("top_p", 1.0),
                                 p.get("top_k", 0), p.get("min_p", 0.0),
@@ -417,12 +448,9 @@ class ShardRuntime:
                                 int(p.get("top_logprobs", 0)), len(nonce_ids),
                                 p.get("repetition_penalty", 1.0),
                                 p.get("presence_penalty", 0.0),
-                                p.get("frequency_penalty", 0.0))
+                                p.get("frequency_penalty", 0.0), 0, 0,
+                                len(pairs))
             import torch.distributed as dist
-            payload = torch.cat([
-                tokens.flatten().to(self._comm_device()),
-                torch.tensor(stop_ids + nonce_ids, dtype=torch.int64,
-                             device=self._comm_device())])
             dist.broadcast(payload, src=0)
         self._execute_infer(nonce, tokens, max_tokens, stop_ids, p)
 
@@ -430,17 +458,21 @@ class ShardRuntime:
         import torch.distributed as dist
         ex = self.executor
         T, max_tokens, n_stop = int(cmd[1]), int(cmd[2]), int(cmd[3])
-        n_nonce = int(cmd[10])
+        n_nonce, n_bias = int(cmd[10]), int(cmd[16])
         p = {"temperature": cmd[4], "top_p": cmd[5], "top_k": int(cmd[6]),
              "min_p": cmd[7], "logprobs": bool(cmd[8]),
              "top_logprobs": int(cmd[9]), "repetition_penalty": cmd[11],
              "presence_penalty": cmd[12], "frequency_penalty": cmd[13]}
-        payload = torch.zeros(T + n_stop + n_nonce, dtype=torch.int64,
-                              device=self._comm_device())
+        payload = torch.zeros(T + n_stop + n_nonce + 2 * n_bias,
+                              dtype=torch.int64, device=self._comm_device())
         dist.broadcast(payload, src=0)
         tokens = payload[:T].view(1, 1, T).cpu()
         stop_ids = payload[T:T + n_stop].tolist()
-        nonce = bytes(payload[T + n_stop:].tolist()).decode("utf-8", "replace")
+        e = T + n_stop + n_nonce
+        nonce = bytes(payload[T + n_stop:e].tolist()).decode("utf-8",
+                                                             "replace")
+        p["logit_bias"] = list(self._bias_from_payload(
+            payload[e:].tolist(), n_bias).items())
         self._execute_infer(nonce, tokens, max_tokens, stop_ids, p)
 
     def _execute_infer(self, nonce: str, tokens: torch.Tensor,
@@ -458,7 +490,8 @@ class ShardRuntime:
             top_logprobs=int(p.get("top_logprobs", 0)),
             repetition_penalty=float(p.get("repetition_penalty", 1.0)),
             presence_penalty=float(p.get("presence_penalty", 0.0)),
-            frequency_penalty=float(p.get("frequency_penalty", 0.0))),
+            frequency_penalty=float(p.get("frequency_penalty", 0.0)),
+            logit_bias=dict(self._bias_pairs(p)) or None),
             seed=p.get("seed"))
         # pad the single sequence to the executor's batch width
         B = ex.mb_size
@@ -613,7 +646,9 @@ class ShardRuntime:
             top_logprobs=int(p.get("top_logprobs", 0)),
             repetition_penalty=float(p.get("repetition_penalty", 1.0)),
             presence_penalty=float(p.get("presence_penalty", 0.0)),
-            frequency_penalty=float(p.get("frequency_penalty", 0.0)))
+            frequency_penalty=float(p.get("frequency_penalty", 0.0)),
+            logit_bias=dict(self._bias_pairs(p)) or None)
+        pairs = list((cfg.logit_bias or {}).items())
         stop_ids = list(frame.get("stop_ids", []))
         max_tokens = int(frame.get("max_tokens", 128))
         nonce = frame.get("nonce", "")
@@ -621,6 +656,12 @@ class ShardRuntime:
         seed = p.get("seed")
         if ex.world > 1:
             import torch.distributed as dist
+            # built first: nothing may raise between the two broadcasts
+            payload = torch.cat([
+                tokens.flatten().to(self._comm_device()),
+                torch.tensor(stop_ids + nonce_ids
+                             + self._bias_payload(pairs), dtype=torch.int64,
+                             device=self._comm_device())])
             self._broadcast_cmd(CMD_SLOT_ADMIT, si, T, max_tokens,
                                 len(stop_ids), len(nonce_ids),
                                 cfg.temperature, cfg.top_p, cfg.top_k,
@@ -628,11 +669,8 @@ class ShardRuntime:
                                 -1.0 if seed is None else int(seed),
                                 1.0 if cfg.logprobs else 0.0,
                                 cfg.top_logprobs, cfg.repetition_penalty,
-                                cfg.presence_penalty, cfg.frequency_penalty)
-            payload = torch.cat([
-                tokens.flatten().to(self._comm_device()),
-                torch.tensor(stop_ids + nonce_ids, dtype=torch.int64,
-                             device=self._comm_device())])
+                                cfg.presence_penalty, cfg.frequency_penalty,
+                                len(pairs))
             dist.broadcast(payload, src=0)
         self._slot_admit_exec(si, tokens.view(-1), max_tokens, stop_ids,
                               nonce, cfg, seed)
@@ -649,12 +687,17 @@ class ShardRuntime:
                              presence_penalty=cmd[14],
                              frequency_penalty=cmd[15])
         seed = None if cmd[10] < 0 else int(cmd[10])
-        payload = torch.zeros(T + n_stop + n_nonce, dtype=torch.int64,
-                              device=self._comm_device())
+        n_bias = int(cmd[16])
+        payload = torch.zeros(T + n_stop + n_nonce + 2 * n_bias,
+                              dtype=torch.int64, device=self._comm_device())
         dist.broadcast(payload, src=0)
         tokens = payload[:T].cpu()
         stop_ids = payload[T:T + n_stop].tolist()
-        nonce = bytes(payload[T + n_stop:].tolist()).decode("utf-8", "replace")
+        e = T + n_stop + n_nonce
+        nonce = bytes(payload[T + n_stop:e].tolist()).decode("utf-8",
+                                                             "replace")
+        cfg.logit_bias = self._bias_from_payload(payload[e:].tolist(),
+                                                 n_bias) or None
         self._slot_admit_exec(si, tokens, max_tokens, stop_ids, nonce, cfg,
                               seed)
 
@@ -695,7 +738,8 @@ class ShardRuntime:
         if ex.is_last:
             from ..core.sampler import Sampler
             tok, lp, tops = Sampler(cfg, generator=gen).sample(
-                logits.float(), self._row_sampler.seen_rows(si))
+                logits, self._row_sampler.seen_rows(si),
+                self._row_sampler.bias_rows(si))
             t0_t[0] = int(tok[0])
             if lp is not None:
                 lp0 = float(lp[0])
@@ -746,8 +790,9 @@ class ShardRuntime:
         self._row_sampler.reset_counts(si)
         tok, lp, tops = Sampler(st["cfg"],
                                 generator=self._row_sampler.gens[si]
-                                ).sample(logits.float(),
-                                         self._row_sampler.seen_rows(si))
+                                ).sample(logits,
+                                         self._row_sampler.seen_rows(si),
+                                         self._row_sampler.bias_rows(si))
         t0 = int(tok[0])
         lp0 = float(lp[0]) if lp is not None else None
         tops0 = tops[0] if tops else None
