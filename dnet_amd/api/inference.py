@@ -37,7 +37,9 @@ def decoding_params(request: ChatRequestModel) -> dict:
         "presence_penalty": request.presence_penalty,
         "frequency_penalty": request.frequency_penalty,
         "logprobs": request.logprobs,
-        "top_logprobs": request.top_logprobs}
+        "top_logprobs": request.top_logprobs,
+        # false: no prefix-cache lookup and no insert for this request
+        "cache_prompt": request.cache_prompt}
     if request.logit_bias:
         # pairs, not a map: msgpack rejects integer map keys on unpack
         params["logit_bias"] = [[int(k), float(v)]
@@ -95,6 +97,7 @@ class InferenceManager:
         t_start = time.perf_counter()
         ttfb_ms = None
         n_tokens = 0
+        cached_tokens = None    # set by the first token frame, if reported
         finish_reason = "stop"
         # OpenAI `stop` strings: matched API-side in the detokenized text
         # (reference ignores them silently — advisor r1). Text that could
@@ -144,6 +147,8 @@ class InferenceManager:
                 n_tokens += 1
                 if ttfb_ms is None:
                     ttfb_ms = (time.perf_counter() - t_start) * 1e3
+                if cached_tokens is None and "cached_tokens" in frame:
+                    cached_tokens = int(frame["cached_tokens"])
                 is_stop = tid in self.mm.stop_ids
                 hit_stop_str = False
                 if not is_stop:
@@ -189,6 +194,8 @@ class InferenceManager:
         usage = UsageModel(prompt_tokens=len(prompt_ids),
                            completion_tokens=n_tokens,
                            total_tokens=len(prompt_ids) + n_tokens)
+        if cached_tokens is not None:
+            usage.prompt_tokens_details = {"cached_tokens": cached_tokens}
         metrics = None
         if request.profile:
             gen_ms = total_ms - (ttfb_ms or 0.0)
@@ -198,6 +205,8 @@ class InferenceManager:
                 "tps_overall": n_tokens / (total_ms / 1e3) if total_ms else 0,
                 "tps_decoding": ((n_tokens - 1) / (gen_ms / 1e3)
                                  if gen_ms > 0 and n_tokens > 1 else 0)}
+            if cached_tokens is not None:
+                metrics["cached_tokens"] = cached_tokens
         yield ChatChunkModel(
             id=nonce, model=request.model,
             choices=[StreamChoice(delta=ChoiceDelta(),

@@ -50,7 +50,8 @@ class ModelManager:
     async def load_model(self, topology: TopologyInfo, entry: CatalogEntry,
                          quant: str = "", max_batch: int = 1,
                          max_seq: int = 4096,
-                         api_callback_address: str = "") -> None:
+                         api_callback_address: str = "",
+                         prefix_cache: int = 0) -> None:
         cfg = resolve_model_config(entry, quant)
         self.config = cfg
         world = len(topology.assignments)
@@ -80,7 +81,8 @@ class ModelManager:
                     master_port=topology.master_port,
                     gpu_index=max(a.gpu_index, 0),
                     max_batch=max_batch, max_seq=max_seq,
-                    quant=quant or entry.quant)
+                    quant=quant or entry.quant,
+                    prefix_entries=prefix_cache)
                 posts.append(client.post(
                     f"http://{dev.local_ip}:{dev.server_port}/load_model",
                     json=req.model_dump()))

@@ -8,7 +8,7 @@ import time
 import uuid
 from typing import Any, Optional
 
-from pydantic import BaseModel, Field, field_validator
+from pydantic import BaseModel, Field, field_validator, model_serializer
 
 
 class ChatMessage(BaseModel):
@@ -41,6 +41,9 @@ class ChatRequestModel(BaseModel):
     top_logprobs: int = 0
     profile: bool = False            # emit metrics in the final chunk
     n: int = 1
+    # false: this request neither reads nor feeds the shard's prompt-prefix
+    # KV cache (no effect when the cache is off)
+    cache_prompt: bool = True
 
     @field_validator("logit_bias")
     @classmethod
@@ -71,6 +74,18 @@ class UsageModel(BaseModel):
     prompt_tokens: int = 0
     completion_tokens: int = 0
     total_tokens: int = 0
+    # OpenAI shape {"cached_tokens": n}; set only when the shard reported a
+    # prefix-cache lookup for the request
+    prompt_tokens_details: Optional[dict] = None
+
+    @model_serializer(mode="wrap")
+    def _drop_unset_details(self, handler):
+        # the key is absent, not null, when nothing was reported: responses
+        # stay byte-identical to a server without a prefix cache
+        d = handler(self)
+        if d.get("prompt_tokens_details") is None:
+            d.pop("prompt_tokens_details", None)
+        return d
 
 
 class ChoiceDelta(BaseModel):
@@ -162,3 +177,6 @@ class APILoadModelRequest(BaseModel):
     max_batch: int = 8
     max_seq: int = 4096
     warmup: bool = False
+    # prompt-prefix KV cache entries per shard (0 = off; needs
+    # max_batch > 1 on a single-rank ring)
+    prefix_cache: int = 0

@@ -123,7 +123,7 @@ def build_api_app(state: ApiState) -> FastAPI:
             await s.models.load_model(
                 s.cluster.topology, entry, quant=req.quant,
                 max_batch=req.max_batch, max_seq=req.max_seq,
-                api_callback_address=cb)
+                api_callback_address=cb, prefix_cache=req.prefix_cache)
         except Exception as e:
             log.exception("load_model failed")
             raise HTTPException(500, str(e))
@@ -163,7 +163,7 @@ def build_api_app(state: ApiState) -> FastAPI:
         await s.models.load_model(
             s.cluster.topology, entry, quant=req.quant,
             max_batch=req.max_batch, max_seq=req.max_seq,
-            api_callback_address=cb)
+            api_callback_address=cb, prefix_cache=req.prefix_cache)
         head = s.cluster.get_head_node()
         s.inference.connect_head(head.local_ip, head.shard_port, cb)
         return {"status": "ok", "excluded": sorted(s.cluster.excluded),

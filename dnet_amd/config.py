@@ -69,6 +69,11 @@ class ComputeSettings(BaseModel):
 class KVCacheSettings(BaseModel):
     bits: int = 16                   # 16 = bf16 (8/4-bit quantized KV later)
     group: int = 64
+    # prompt-prefix KV cache (slot-scheduled serving on one rank): number
+    # of store entries, each one max_seq rows of KV (0 = off), and the
+    # shortest shared prefix worth a copy instead of a re-prefill
+    prefix_entries: int = 0
+    prefix_min: int = 32
 
 
 class TransportSettings(BaseModel):

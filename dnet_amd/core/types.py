@@ -83,3 +83,6 @@ class ShardLoadModelRequest(BaseModel):
     max_seq: int = 4096
     quant: str = ""                   # "" | "int8-g128" | ...
     warmup: bool = False
+    # prompt-prefix KV store entries (0 = the DNET_KV_PREFIX_ENTRIES
+    # default, itself 0 = off)
+    prefix_entries: int = 0

@@ -326,6 +326,14 @@ class KVCache:
     def reset(self):
         self.pos.zero_()
 
+    def planes(self) -> list:
+        """The cache tensors, each [L, B, H, S, row]: what
+        ``ops.kv_copy_rows`` moves between a slot and a prefix-store
+        entry."""
+        if self.kscale is not None:
+            return [self.k, self.v, self.kscale, self.vscale]
+        return [self.k, self.v]
+
     def nbytes(self) -> int:
         n = 2 * self.k.numel() * self.k.element_size()
         if self.kscale is not None:

@@ -47,6 +47,10 @@ class MLAKVCache(KVCache):
         self.smax = smax
         self.batch = batch
 
+    def planes(self) -> list:
+        # latent planes are [L, B, S, row]: H = 1 for ops.kv_copy_rows
+        return [self.ckv, self.kpe] if self.latent else [self.k, self.v]
+
     def nbytes(self) -> int:
         if self.latent:
             return 2 * (self.ckv.numel() + self.kpe.numel())

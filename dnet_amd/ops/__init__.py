@@ -466,6 +466,25 @@ def logprobs_rows(logits: torch.Tensor, tok: torch.Tensor,
     return ref.logprobs_rows(logits, tok, n_top, K, logp, topv, topi)
 
 
+def kv_copy_rows(dst_planes, dst_b: int, src_planes, src_b: int, r0: int,
+                 r1: int) -> None:
+    """Copy KV rows [r0, r1) of batch index `src_b` to the same rows of
+    batch index `dst_b`, for every plane (``KVCache.planes()``), local
+    layer and head. A plane is a contiguous cache tensor
+    [L, B, (H,) S, row]; L, H, S and row bytes must agree between a src
+    plane and its dst plane, B may differ, and src may be dst itself with
+    two different batch indices. One launch on the current stream for all
+    planes (none when r0 == r1); eager only, never inside graph capture.
+    A violated precondition raises before anything is launched."""
+    dst_planes, src_planes = list(dst_planes), list(src_planes)
+    if dst_planes and dst_planes[0].is_cuda:
+        _native().kv_copy_rows(dst_planes, int(dst_b), src_planes,
+                               int(src_b), int(r0), int(r1))
+        return
+    ref.kv_copy_rows(dst_planes, int(dst_b), src_planes, int(src_b),
+                     int(r0), int(r1))
+
+
 def dequant_mxfp4(w: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     """MXFP4 row-major (nibbles [N, K/2] + e8m0 [N, K/32]) -> bf16."""
     if w.is_cuda and has_native():

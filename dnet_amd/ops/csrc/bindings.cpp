@@ -76,6 +76,9 @@ void sample_rows(torch::Tensor logits, torch::Tensor temp, torch::Tensor top_k,
 void logprobs_rows(torch::Tensor logits, torch::Tensor tok,
                    torch::Tensor n_top, torch::Tensor logp, torch::Tensor topv,
                    torch::Tensor topi);
+void kv_copy_rows(std::vector<torch::Tensor> dst_planes, int64_t dst_b,
+                  std::vector<torch::Tensor> src_planes, int64_t src_b,
+                  int64_t r0, int64_t r1);
 }  // namespace dnet
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -137,4 +140,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = c10::nullopt, py::arg("bias_on") = c10::nullopt);
   m.def("logprobs_rows", &dnet::logprobs_rows,
         "chosen-token and ordered top-K logprobs per row, sort-free");
+  m.def("kv_copy_rows", &dnet::kv_copy_rows,
+        "copy KV rows [r0, r1) between batch indices of two caches, "
+        "all planes/layers/heads in one launch",
+        py::arg("dst_planes"), py::arg("dst_b"), py::arg("src_planes"),
+        py::arg("src_b"), py::arg("r0"), py::arg("r1"));
 }

@@ -650,3 +650,56 @@ def logprobs_rows(logits: torch.Tensor, tok: torch.Tensor,
         topi[b, n:] = -1
         topv[b, n:] = float("nan")
     return logp, topv, topi
+
+
+def _kv_plane_geom(t: torch.Tensor):
+    """A cache plane [L, B, (H...), S, row] -> (L, B, H, S, row_bytes); the
+    dims between B and S fold into H (MLA latent planes have none: H = 1)."""
+    if t.dim() < 4:
+        raise ValueError("kv_copy_rows: plane must be [L, B, (H,) S, row]")
+    H = 1
+    for n in t.shape[2:-2]:
+        H *= int(n)
+    return (int(t.shape[0]), int(t.shape[1]), H, int(t.shape[-2]),
+            int(t.shape[-1]) * t.element_size())
+
+
+def kv_copy_rows(dst_planes, dst_b: int, src_planes, src_b: int, r0: int,
+                 r1: int) -> None:
+    """Rows [r0, r1) of batch index `src_b` of every src plane -> the same
+    rows of batch index `dst_b` of the matching dst plane, for every layer
+    and head: the contract of the HIP row-copy kernel, as one slice
+    assignment per plane. L, H, S and row_bytes must agree between a src
+    plane and its dst plane, B may differ; a violated precondition raises
+    before anything is written."""
+    if not 1 <= len(dst_planes) <= 4 or len(src_planes) != len(dst_planes):
+        raise ValueError("kv_copy_rows: 1..4 planes, same count on both sides")
+    for d, s in zip(dst_planes, src_planes):
+        if not (d.is_contiguous() and s.is_contiguous()):
+            raise ValueError("kv_copy_rows: planes must be contiguous")
+        if d.dtype != s.dtype or d.device != s.device:
+            raise ValueError("kv_copy_rows: plane dtype/device mismatch")
+        Ld, Bd, Hd, Sd, rbd = _kv_plane_geom(d)
+        Ls, Bs, Hs, Ss, rbs = _kv_plane_geom(s)
+        if (Ld, Hd, Sd, rbd) != (Ls, Hs, Ss, rbs):
+            raise ValueError("kv_copy_rows: src/dst geometry "
+                             "(L, H, S, row_bytes) differs")
+        if not 0 <= r0 <= r1 <= Sd:
+            raise ValueError("kv_copy_rows: need 0 <= r0 <= r1 <= S")
+        if not 0 <= dst_b < Bd:
+            raise ValueError("kv_copy_rows: dst_b out of range")
+        if not 0 <= src_b < Bs:
+            raise ValueError("kv_copy_rows: src_b out of range")
+        sp, dp = s.data_ptr(), d.data_ptr()
+        if (sp < dp + d.numel() * d.element_size()
+                and dp < sp + s.numel() * s.element_size()):
+            if sp != dp or Bs != Bd:
+                raise ValueError("kv_copy_rows: src and dst overlap without "
+                                 "being one plane")
+            if src_b == dst_b:
+                raise ValueError("kv_copy_rows: src_b == dst_b on an "
+                                 "aliased plane")
+    if r0 == r1:
+        return
+    for d, s in zip(dst_planes, src_planes):
+        d[:, dst_b, ..., r0:r1, :] = s[:, src_b, ..., r0:r1, :]

@@ -448,19 +448,24 @@ class RingExecutor:
     # ------------- slot-batched serving (continuous batching) -------------
 
     def prefill_slot(self, si: int, tokens: torch.Tensor,
-                     chunk: int = 2048):
+                     chunk: int = 2048, p_start: int = 0):
         """Collective single-slot prefill through the ring: one sequence
         flows stage to stage (position-chunked to bound activations) while
         other slots keep decoding state. ``tokens`` [T] int64 (significant
         on the first stage). Returns the last-position logits [1, V] on
-        the LAST stage, else None."""
+        the LAST stage, else None.
+
+        ``p_start`` > 0 (prefix cache hit): rows [0, p_start) of the slot
+        already hold the KV of ``tokens[:p_start]``; only positions
+        [p_start, T) are computed, attending to those rows."""
         T = int(tokens.shape[-1])
+        assert 0 <= p_start < T, "at least one position must be prefilled"
         H = self.cfg.hidden_size
         kvslot = self.kvs[0].slot(si)
         kvslot.pos.fill_(0)
         step = chunk if 0 < chunk < T else T
         h = None
-        for p0 in range(0, T, step):
+        for p0 in range(p_start, T, step):
             p1 = min(p0 + step, T)
             h = None
             for r in range(self.rounds):

@@ -74,6 +74,10 @@ class ShardRuntime:
         self._callback: Optional[SyncWireClient] = None
         self.slots: Optional[list] = None   # continuous batching (world==1)
         self._cancelled: dict = {}          # nonce -> ts, cancelled by API
+        # prompt-prefix KV cache (slot mode, one rank): host index + a
+        # second KV cache object whose batch rows are the store entries
+        self.prefix = None
+        self.prefix_kv = None
         self._stop = threading.Event()
         self.status = "idle"
         self.last_error = ""
@@ -214,6 +218,23 @@ class ShardRuntime:
             # and re-admitted and must not deliver the stale token under
             # the new request's nonce
             self._slot_gen = [0] * req.max_batch
+        self.prefix = self.prefix_kv = None
+        want = req.prefix_entries or self.settings.kv_cache.prefix_entries
+        if want > 0:
+            if self._prefix_supported(req, ex.cp):
+                from ..core.prefix_cache import PrefixCache
+                # same class, kv_bits and geometry as ex.kvs[0]: one batch
+                # row of the store per entry
+                self.prefix_kv = ex.model.make_kv_cache(want, req.max_seq)
+                self.prefix = PrefixCache(
+                    want, self.settings.kv_cache.prefix_min)
+                log.info("[PROFILE][PREFIX] store entries=%d rows=%d "
+                         "min_prefix=%d bytes=%d", want, req.max_seq,
+                         self.prefix.min_prefix, self.prefix_kv.nbytes())
+            else:
+                log.info("prefix cache requested (entries=%d) but it needs "
+                         "slot-scheduled serving on one rank (max_batch > 1,"
+                         " world_size 1, cp 1): staying off", want)
         self.load_req = req
         self.model_name = req.model_name or req.model_path
         # one emitter per ring: the grp-rank-0 member of the last stage
@@ -287,6 +308,8 @@ class ShardRuntime:
         import torch.distributed as dist
         self.executor = None
         self.slots = None
+        self.prefix = None
+        self.prefix_kv = None       # freed with the model (empty_cache below)
         self._pending = None
         self.load_req = None
         self.model_name = ""
@@ -542,6 +565,8 @@ class ShardRuntime:
                     self._cancelled.pop(st["nonce"], None)
                     if ex.world > 1:
                         self._broadcast_cmd(CMD_SLOT_CANCEL, i)
+                    # stop strings end most chats through here
+                    self._prefix_retire(i, st)
                     self.slots[i] = None
                     self._row_sampler.clear_row(i)
                     self._park_dev[i] = True
@@ -673,7 +698,8 @@ class ShardRuntime:
                                 len(pairs))
             dist.broadcast(payload, src=0)
         self._slot_admit_exec(si, tokens.view(-1), max_tokens, stop_ids,
-                              nonce, cfg, seed)
+                              nonce, cfg, seed,
+                              cache_prompt=bool(p.get("cache_prompt", True)))
 
     def _slot_admit_follower(self, cmd) -> None:
         import torch.distributed as dist
@@ -702,19 +728,31 @@ class ShardRuntime:
                               seed)
 
     def _slot_admit_exec(self, si, tokens, max_tokens, stop_ids, nonce,
-                         cfg, seed=None) -> None:
+                         cfg, seed=None, cache_prompt: bool = True) -> None:
         """Collective slot admit (every rank): single-slot ring prefill,
         sample on the last stage, broadcast the first token, register the
-        slot state identically everywhere."""
+        slot state identically everywhere.
+
+        With the prefix cache on, the longest cached prefix of the prompt
+        is copied into the slot and only the rest is prefilled."""
         ex = self.executor
         self._slot_gen[si] += 1
-        max_tokens = max(1, min(max_tokens,
-                                ex.smax - int(tokens.shape[-1])))
+        T = int(tokens.shape[-1])
+        max_tokens = max(1, min(max_tokens, ex.smax - T))
         gen = self._row_sampler.set_row(si, cfg, seed)
-        # the whole prompt is known here, also for a chunked prefill
+        # the whole prompt is known here, also for a chunked prefill (and
+        # for a prefix-cache hit: penalties see every prompt token)
         self._row_sampler.note_prompt(si, tokens)
+        # hist: prompt + emitted tokens as a host list while the request
+        # may feed the prefix cache (row j of the slot = KV of hist[j])
+        hist, n_hit = None, 0
+        first_extra = None if self.prefix is None else {"cached_tokens": 0}
+        if self.prefix is not None and cache_prompt:
+            hist = [int(t) for t in tokens.tolist()]
+            n_hit = self._prefix_load(si, hist, nonce)
+            first_extra["cached_tokens"] = n_hit
         chunk = int(os.environ.get("DNET_PREFILL_CHUNK", "2048"))
-        if ex.world == 1 and int(tokens.shape[-1]) > chunk:
+        if ex.world == 1 and T - n_hit > chunk:
             # long prompt: admit in "prefill" state — the tick loop feeds
             # one chunk per iteration between decode steps (slot stays
             # PARKED until the prefill completes)
@@ -726,13 +764,18 @@ class ShardRuntime:
             # the first prefill chunk
             ex.kvs[0].pos[si] = ex.smax - 1
             self.slots[si] = {"state": "prefill", "tokens": tokens,
-                              "p0": 0, "cfg": cfg, "nonce": nonce,
+                              "p0": n_hit, "cfg": cfg, "nonce": nonce,
                               "produced": 0, "max_tokens": max_tokens,
-                              "stop_ids": set(stop_ids)}
+                              "stop_ids": set(stop_ids), "T": T,
+                              "hist": hist, "first_extra": first_extra}
             log.info("[PROFILE][SLOT] admit slot=%d nonce=%s prompt=%d "
                      "(chunked)", si, nonce[:18], int(tokens.shape[-1]))
             return
-        logits = ex.prefill_slot(si, tokens)
+        logits = ex.prefill_slot(si, tokens, p_start=n_hit)
+        if hist is not None:
+            # prompt rows are final: share them now, while this request
+            # is still generating (concurrent requests, one system prompt)
+            self._prefix_save(si, hist, T)
         t0_t = torch.zeros(1, dtype=torch.int64, device=self._comm_device())
         lp0 = tops0 = None
         if ex.is_last:
@@ -753,11 +796,15 @@ class ShardRuntime:
             # the sampling rank counted it in Sampler.sample
             self._row_sampler.note_token(si, t0)
         st = {"nonce": nonce, "produced": 1, "max_tokens": max_tokens,
-              "stop_ids": set(stop_ids)}
+              "stop_ids": set(stop_ids), "T": T, "hist": hist}
+        if hist is not None:
+            hist.append(t0)
         done = t0 in st["stop_ids"] or max_tokens <= 1
         if ex.is_last:
             self._emit_token(nonce, t0, finished=done, logprob=lp0,
-                             tops=tops0)
+                             tops=tops0, extra=first_extra)
+        # done at the first token: the entry would be rows [0, T + 1 - 1),
+        # exactly what the prompt insert above stored
         if not done:
             self.slots[si] = st
             self._park_dev[si] = False
@@ -783,6 +830,10 @@ class ShardRuntime:
         if p1 < T:
             return
         kvslot.pos.fill_(T)
+        hist = st.get("hist")
+        if hist is not None:
+            # last chunk: the prompt rows are final, share them now
+            self._prefix_save(si, hist, T)
         logits = ex.model.normalize_project(h[:, -1].contiguous())
         from ..core.sampler import Sampler
         # decode steps of the other slots sampled (and counted) this parked
@@ -802,11 +853,14 @@ class ShardRuntime:
         self._park_dev[si] = False
         self._free_dev[si] = False
         st.pop("tokens")
+        if hist is not None:
+            hist.append(t0)
         done = t0 in st["stop_ids"] or st["max_tokens"] <= 1
         if ex.is_last:
             self._emit_token(st["nonce"], t0, finished=done, logprob=lp0,
-                             tops=tops0)
+                             tops=tops0, extra=st.pop("first_extra", None))
         if done:
+            # (nothing more to store: rows [0, T) went in above)
             self.slots[si] = None
             self._row_sampler.clear_row(si)
             self._park_dev[si] = True
@@ -902,7 +956,10 @@ class ShardRuntime:
                 tops = {int(ti_l[i][j]): float(tv_l[i][j]) for j in range(k)}
             self._emit_token(st["nonce"], t, finished=done, logprob=lp,
                              tops=tops)
+            if st.get("hist") is not None:
+                st["hist"].append(t)
             if done:
+                self._prefix_retire(i, st)
                 self.slots[i] = None
                 self._row_sampler.clear_row(i)
                 self._park_dev[i] = True
@@ -910,14 +967,94 @@ class ShardRuntime:
 
     _emit_s = 0.0
 
+    # ---------- prompt-prefix KV cache ----------
+    #
+    # Ordering: every copy below is enqueued on the stream the decode
+    # steps and prefills run on, at the moment the host decides it, so the
+    # stream order is the data order. The hazard is on the SAVE side: a
+    # freed slot is parked at pos 0 and every later decode step appends a
+    # dummy row there, so its row 0 is destroyed a couple of ticks after
+    # the slot retires. _prefix_retire therefore runs where retirement is
+    # detected (the `done` branch of _slot_emit, the cancel sweep at the
+    # top of _slots_tick), i.e. before the next _slot_step_launch, whose
+    # end-of-step mask is what moves the row to pos 0, and before the slot
+    # can be re-admitted. On the pipelined path one more step is already
+    # in flight when `done` is seen: it appends the KV of the last emitted
+    # token at row T + m - 1, outside the saved range [0, T + m - 1).
+
+    @staticmethod
+    def _prefix_supported(req: ShardLoadModelRequest, cp: int = 1) -> bool:
+        """v1: slot-scheduled serving on one rank."""
+        return req.max_batch > 1 and req.world_size == 1 and cp == 1
+
+    def _prefix_load(self, si: int, prompt: list, nonce: str) -> int:
+        """Copy the longest cached prefix of `prompt` into slot `si`;
+        returns its length (0 on a miss)."""
+        from .. import ops
+        pc = self.prefix
+        e, n = pc.lookup(prompt)
+        if n > 0:
+            ops.kv_copy_rows(self.executor.kvs[0].planes(), si,
+                             self.prefix_kv.planes(), e, 0, n)
+            log.info("[PROFILE][PREFIX] hit slot=%d nonce=%s entry=%d "
+                     "cached=%d prompt=%d", si, nonce[:18], e, n,
+                     len(prompt))
+        else:
+            log.info("[PROFILE][PREFIX] miss slot=%d nonce=%s prompt=%d",
+                     si, nonce[:18], len(prompt))
+        return n
+
+    def _prefix_save(self, si: int, hist: list, rows: int) -> None:
+        """Store rows [0, rows) of slot `si` (the KV of hist[:rows]): only
+        the rows the chosen entry does not hold yet are copied. Never the
+        park row smax - 1; prefixes shorter than min_prefix could never be
+        hit and are not stored."""
+        from .. import ops
+        pc = self.prefix
+        rows = min(rows, self.executor.smax - 1, len(hist))
+        if rows < pc.min_prefix:
+            return
+        ev = pc.evictions
+        e, have = pc.plan_insert(hist[:rows])
+        if e < 0:
+            return
+        if pc.evictions != ev:
+            log.info("[PROFILE][PREFIX] evict entry=%d", e)
+        try:
+            ops.kv_copy_rows(self.prefix_kv.planes(), e,
+                             self.executor.kvs[0].planes(), si, have, rows)
+        except Exception:
+            pc.drop(e)      # the index must never promise rows not copied
+            raise
+        log.info("[PROFILE][PREFIX] insert slot=%d entry=%d rows=%d "
+                 "copied=%d", si, e, rows, rows - have)
+
+    def _prefix_retire(self, si: int, st: dict) -> None:
+        """A slot retires after m emitted tokens: rows [0, T + m - 1) hold
+        the KV of prompt + generated[:m - 1] (the last emitted token's KV
+        is not part of the entry). See the ordering note above."""
+        hist = st.get("hist")
+        if (self.prefix is None or hist is None
+                or st.get("state") == "prefill"):
+            return
+        self._prefix_save(si, hist, st["T"] + st["produced"] - 1)
+
+    def prefix_stats(self) -> dict:
+        """Prefix-cache counters for /health ({} when the cache is off).
+        Read from HTTP threads: a snapshot of plain ints."""
+        pc = self.prefix
+        return pc.stats() if pc is not None else {}
+
     def _emit_token(self, nonce: str, token_id: int, finished: bool = False,
-                    logprob=None, tops=None):
+                    logprob=None, tops=None, extra: Optional[dict] = None):
         ex = self.executor
         if self._callback is None:
             return
         t0 = time.perf_counter()
         frame = {"t": "token", "nonce": nonce, "token_id": token_id,
                  "ts_ms": int(time.time() * 1e3), "finished": finished}
+        if extra:
+            frame.update(extra)     # first frame: {"cached_tokens": n}
         if logprob is None and ex.last_logprob is not None:
             logprob = float(ex.last_logprob[0])     # legacy serial path
         if tops is None and ex.last_tops is not None:

@@ -31,6 +31,7 @@ class HealthResponse(BaseModel):
     error: str = ""
     rank: int = -1                 # rank in the active ring (-1 = none)
     xgmi: dict = {}                # all-pairs link matrix ("i-j" -> ms/GBps)
+    prefix_cache: dict = {}        # prefix-cache counters ({} = cache off)
 
 
 class MeasureLatencyRequest(BaseModel):
@@ -49,7 +50,8 @@ def build_shard_app(rt: ShardRuntime) -> FastAPI:
                               queue_depth=rt.infer_q.qsize(),
                               error=rt.last_error,
                               rank=getattr(rt, "rank", -1),
-                              xgmi=getattr(rt, "link_matrix", {}) or {})
+                              xgmi=getattr(rt, "link_matrix", {}) or {},
+                              prefix_cache=rt.prefix_stats())
 
     @app.post("/load_model")
     def load_model(req: ShardLoadModelRequest) -> dict:
