@@ -685,10 +685,12 @@ class RingModel:
         len_t = kv.pos + 1  # attend over lengths including the token being written
         delta = None
         self._mlp_defer_ok = True   # only this loop consumes DEFERRED
+        self._deferred_splits = 0   # slices behind the current DEFERRED
         for lid in layer_ids:
             lw = self._layer(lid)
             if delta is ops.DEFERRED:
-                y = ops.rmsnorm_f32_scratch(h, lw.attn_norm, c.rms_eps)
+                y = ops.rmsnorm_f32_scratch(h, lw.attn_norm, c.rms_eps,
+                                            self._deferred_splits)
             else:
                 y = ops.rmsnorm(delta if delta is not None else h,
                                 h if delta is not None else None,
@@ -771,7 +773,7 @@ class RingModel:
                     self._profile_layer_sync(lid)
         self._mlp_defer_ok = False
         if delta is ops.DEFERRED:
-            ops.resid_add_scratch(h)
+            ops.resid_add_scratch(h, self._deferred_splits)
         else:
             h.add_(delta)
         return h
@@ -810,10 +812,11 @@ class RingModel:
                 and dl.bias is None and self.tp_size == 1
                 and 2 < a.shape[0] <= 64
                 and ops.linear_will_defer(a, dl.w, dl.group, dl.bits)):
-            # leave the down projection un-combined in the f32 scratch;
+            # leave the down projection un-combined in the f32 partials;
             # the decode loop's next RMSNorm (or the final residual add)
-            # consumes + re-zeroes it
-            ops.gemv_defer(a, dl.w, dl.scales, dl.group, dl.bits)
+            # sums its slices
+            self._deferred_splits = ops.gemv_defer(a, dl.w, dl.scales,
+                                                   dl.group, dl.bits)
             return ops.DEFERRED
         return dl(a)
 

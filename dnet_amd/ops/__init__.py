@@ -50,10 +50,12 @@ def _native():
 def set_reproducible(on: bool) -> None:
     """Opt-in bit-reproducible decode GEMMs (OFF by default).
 
-    The split-k decode GEMM combines its partials with f32 atomics whose
-    arrival order varies, so results differ in the last bit from run to
-    run. When on, partials are rounded to a 2^-16 grid first, which makes
-    the additions exact (order-independent) while sums stay below 2^8 — at
+    The split-k decode GEMM stores one f32 partial per split and its
+    consumer sums them in a fixed order, so two launches already agree
+    bit for bit; what still changes the last bit is the number of splits
+    (a heuristic that may move between builds). When on, partials are
+    rounded to a 2^-16 grid first, which makes the additions exact
+    (independent of order and grouping) while sums stay below 2^8 — at
     the price of an absolute precision floor of 2^-17 per partial. Meant
     for synthetic benchmark runs with O(1) activations whose outputs are
     compared across runs or builds; leave it off for real checkpoints.
@@ -72,22 +74,36 @@ def rmsnorm(x: torch.Tensor, residual: torch.Tensor | None, w: torch.Tensor,
     return ref.rmsnorm(x, residual, w, eps)
 
 
-# split-K f32 scratch, cached per device (max 64 rows x N<8192 cols)
+# Per-device f32 buffers of 64 x 152064 elements each (the largest M=64
+# pass, lm_head-class N).
 _scratch: dict = {}
+_partials: dict = {}
+_SPLITK_ELEMS = 64 * 152064
 
 
 def _get_scratch(device) -> torch.Tensor:
+    """The zero-at-rest f32 buffer of the legacy (splits = 1) consumer
+    mode. No GEMM writes it any more: callers that fill it themselves and
+    run a *_f32 consumer with splits = 1 get it back zeroed."""
     key = str(device)
     if key not in _scratch:
-        # zero-initialized: the split-k path relies on it (the combine
-        # kernel re-zeroes after each use instead of a per-launch memset)
-        # sized for the largest M=64 pass (lm_head-class N): too small a
-        # scratch silently disables split-k (launch_m16 falls back to
-        # sk=1) — measured on gateup N=55296: 864 blocks quantize badly
-        # onto 256 CUs at 3 blocks/CU
-        _scratch[key] = torch.zeros(64 * 152064, dtype=torch.float32,
+        _scratch[key] = torch.zeros(_SPLITK_ELEMS, dtype=torch.float32,
                                     device=device)
     return _scratch[key]
+
+
+def _get_partials(device) -> torch.Tensor:
+    """Split-k partials of the decode GEMM, [sk][M][N] f32: split s stores
+    its whole [M,N] tile into slice s and the consumer sums the slices, so
+    the contents at rest mean nothing and are never cleaned. Too small a
+    buffer silently lowers sk (measured on gateup N=55296 without split-k:
+    864 blocks quantize badly onto 256 CUs at 3 blocks/CU); pick_splitk
+    never asks for more than 8.4 M elements at M <= 64."""
+    key = str(device)
+    if key not in _partials:
+        _partials[key] = torch.empty(_SPLITK_ELEMS, dtype=torch.float32,
+                                     device=device)
+    return _partials[key]
 
 
 def gemv_bf16(x: torch.Tensor, w: torch.Tensor,
@@ -95,7 +111,7 @@ def gemv_bf16(x: torch.Tensor, w: torch.Tensor,
     if x.is_cuda:
         out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
         if x.shape[1] % 64 == 0:
-            _native().gemm_m16(x, w, None, bias, out, _get_scratch(x.device),
+            _native().gemm_m16(x, w, None, bias, out, _get_partials(x.device),
                                0, False, 16)
         else:
             _native().gemv_bf16(x, w, out, bias)
@@ -112,7 +128,7 @@ def gemv_int8(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
     if x.is_cuda:
         out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
         if packed and x.shape[0] > 2:
-            _native().gemm_m16(x, w, scales, bias, out, _get_scratch(x.device),
+            _native().gemm_m16(x, w, scales, bias, out, _get_partials(x.device),
                                group, True, 8)
         else:
             # M<=2: the scalar GEMV reads 16B/lane and hits 4-5.6 TB/s
@@ -129,7 +145,7 @@ def gemv_int4(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
     if x.is_cuda:
         assert packed, "GPU int4 path needs the packed layout"
         out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
-        _native().gemm_m16(x, w, scales, bias, out, _get_scratch(x.device),
+        _native().gemm_m16(x, w, scales, bias, out, _get_partials(x.device),
                            group, True, 4)
         return out
     return ref.gemv_int4(x, w, scales, group, bias)
@@ -235,6 +251,8 @@ _defer_cache: dict = {}
 
 def _will_defer(M: int, N: int, K: int, group: int, bits: int,
                 scratch_elems: int) -> bool:
+    """scratch_elems: capacity of the partials buffer (the legacy scratch
+    has the same size)."""
     key = (M, N, K, group, bits)
     v = _defer_cache.get(key)
     if v is None:
@@ -248,21 +266,21 @@ def gemv_qkv_rope(y: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
                   kcache, vcache, pos, cos, sin, kscale=None, vscale=None,
                   wpos=None):
     """Fused qkv GEMM + RoPE + KV append for the decode path: when the
-    GEMM runs split-k, RoPE reads (and re-zeroes) the f32 scratch
-    directly, applies the qkv bias itself, writes the rotated q to a
+    GEMM runs split-k, RoPE sums the f32 partial slices itself,
+    applies the qkv bias, writes the rotated q to a
     dedicated buffer and k/v straight to the cache — the combine kernel
     and the bf16 k/v round trip disappear from the dependency chain.
     Returns the rotated q [B, nq, d]."""
     B = y.shape[0]
-    scratch = _get_scratch(y.device)
-    if _will_defer(B, w.shape[0], y.shape[1], group, bits, scratch.numel()):
+    part = _get_partials(y.device)
+    if _will_defer(B, w.shape[0], y.shape[1], group, bits, part.numel()):
         out = torch.empty(B, w.shape[0], dtype=y.dtype, device=y.device)
-        deferred = _native().gemm_m16(y, w, scales, None, out, scratch,
-                                      group, True, bits, True)
-        assert deferred, "will_defer disagreed with gemm_m16"
+        sk = _native().gemm_m16(y, w, scales, None, out, part, group, True,
+                                bits, True)
+        assert sk > 1, "will_defer disagreed with gemm_m16"
         q = torch.empty(B, nq, d, dtype=y.dtype, device=y.device)
-        _native().rope_append_f32(scratch, bias, q, nkv, kcache, vcache,
-                                  pos, cos, sin, kscale, vscale, wpos)
+        _native().rope_append_f32(part, bias, q, nkv, kcache, vcache,
+                                  pos, cos, sin, kscale, vscale, wpos, sk)
         return q
     gemv = gemv_int8 if bits == 8 else gemv_int4
     qkv = gemv(y, w, scales, group, bias, True)
@@ -276,58 +294,72 @@ def gemv_qkv_rope(y: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
 
 class _Deferred:
     """Sentinel: the projection's result lives (un-combined, f32) in the
-    split-k scratch; the consumer must read+re-zero it."""
+    split-k partials buffer; the consumer must sum its slices."""
 
 
 DEFERRED = _Deferred()
 
+# slices of the last gemv_defer per device: what a consumer called
+# without an explicit count sums. Read when the consumer is launched (or
+# captured), and handed to the kernel as an argument.
+_deferred_splits: dict = {}
+
 
 def gemv_defer(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
-               group: int, bits: int) -> bool:
-    """Launch the GEMM leaving the f32 split-k result in the scratch
-    (caller checked _will_defer). Returns True."""
+               group: int, bits: int) -> int:
+    """Launch the GEMM leaving its f32 split-k partials un-combined
+    (caller checked _will_defer). Returns the number of slices (> 1),
+    which rmsnorm_f32_scratch / resid_add_scratch take as ``splits``."""
     out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
-    d = _native().gemm_m16(x, w, scales, None, out, _get_scratch(x.device),
-                           group, True, bits, True)
-    assert d, "will_defer disagreed with gemm_m16"
-    return True
+    sk = _native().gemm_m16(x, w, scales, None, out, _get_partials(x.device),
+                            group, True, bits, True)
+    assert sk > 1, "will_defer disagreed with gemm_m16"
+    _deferred_splits[str(x.device)] = sk
+    return sk
 
 
 def rmsnorm_f32_scratch(residual: torch.Tensor, wn: torch.Tensor,
-                        eps: float) -> torch.Tensor:
-    """RMSNorm(+residual) whose x input is the deferred f32 scratch."""
+                        eps: float, splits: int | None = None) -> torch.Tensor:
+    """RMSNorm(+residual) whose x input is the deferred f32 partials
+    (``splits`` slices; default: those of the last gemv_defer)."""
+    if splits is None:
+        splits = _deferred_splits[str(residual.device)]
     y = torch.empty_like(residual)
-    _native().rmsnorm_f32(_get_scratch(residual.device), residual, wn, y,
-                          eps)
+    _native().rmsnorm_f32(_get_partials(residual.device), residual, wn, y,
+                          eps, splits)
     return y
 
 
-def resid_add_scratch(h: torch.Tensor) -> None:
-    _native().resid_add_f32(h, _get_scratch(h.device))
+def resid_add_scratch(h: torch.Tensor, splits: int | None = None) -> None:
+    """h += the deferred f32 partials (see rmsnorm_f32_scratch)."""
+    if splits is None:
+        splits = _deferred_splits[str(h.device)]
+    _native().resid_add_f32(h, _get_partials(h.device), splits)
 
 
 def linear_will_defer(x: torch.Tensor, w: torch.Tensor, group: int,
                       bits: int) -> bool:
     return _will_defer(x.shape[0], w.shape[0], x.shape[1], group, bits,
-                       _get_scratch(x.device).numel())
+                       _get_partials(x.device).numel())
 
 
 def gemv_rmsnorm(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
                  group: int, bits: int, residual: torch.Tensor,
                  wn: torch.Tensor, eps: float) -> torch.Tensor:
     """Fused projection GEMM + RMSNorm(+residual) for the decode path:
-    when the GEMM runs split-k, the norm reads (and re-zeroes) the f32
-    scratch directly — the combine kernel disappears from the chain.
+    when the GEMM runs split-k, the norm sums the f32 partial slices
+    itself — the combine kernel disappears from the chain.
     Updates `residual` in place (residual += proj) like ops.rmsnorm."""
-    scratch = _get_scratch(x.device)
+    part = _get_partials(x.device)
     if _will_defer(x.shape[0], w.shape[0], x.shape[1], group, bits,
-                   scratch.numel()):
+                   part.numel()):
         out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype,
                           device=x.device)
-        _native().gemm_m16(x, w, scales, None, out, scratch, group, True,
-                           bits, True)
+        sk = _native().gemm_m16(x, w, scales, None, out, part, group, True,
+                                bits, True)
+        assert sk > 1, "will_defer disagreed with gemm_m16"
         y = torch.empty_like(residual)
-        _native().rmsnorm_f32(scratch, residual, wn, y, eps)
+        _native().rmsnorm_f32(part, residual, wn, y, eps, sk)
         return y
     gemv = gemv_int8 if bits == 8 else gemv_int4
     o = gemv(x, w, scales, group, None, True)
@@ -338,7 +370,7 @@ def gemv_swiglu(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
                 group: int, bits: int = 8,
                 packed: bool = True) -> torch.Tensor:
     """Fused gate/up GEMM + SwiGLU for the decode path: when the GEMM
-    runs split-k, SwiGLU reads (and re-zeroes) the f32 scratch directly
+    runs split-k, SwiGLU sums the f32 partial slices itself
     instead of going through the f32->bf16 combine kernel — one fewer
     dependent ~5 us kernel per layer per step."""
     if not (x.is_cuda and packed and 2 < x.shape[0] <= 64):
@@ -346,12 +378,12 @@ def gemv_swiglu(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
         return swiglu(gemv(x, w, scales, group, None, packed))
     M, N = x.shape[0], w.shape[0]
     out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-    scratch = _get_scratch(x.device)
-    deferred = _native().gemm_m16(x, w, scales, None, out, scratch, group,
-                                  True, bits, True)
+    part = _get_partials(x.device)
+    sk = _native().gemm_m16(x, w, scales, None, out, part, group, True,
+                            bits, True)
     y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-    if deferred:
-        _native().swiglu_f32(scratch, y, N)
+    if sk:
+        _native().swiglu_f32(part, y, N, sk)
     else:
         _native().swiglu(out, y)
     return y

@@ -4,8 +4,8 @@ namespace py = pybind11;
 
 namespace dnet {
 void rmsnorm_f32(torch::Tensor xf, torch::Tensor residual, torch::Tensor w,
-                 torch::Tensor y, double eps);
-void resid_add_f32(torch::Tensor h, torch::Tensor xf);
+                 torch::Tensor y, double eps, int64_t splits);
+void resid_add_f32(torch::Tensor h, torch::Tensor xf, int64_t splits);
 void rmsnorm(torch::Tensor x, c10::optional<torch::Tensor> residual,
              torch::Tensor w, torch::Tensor y, double eps);
 void gemv_bf16(torch::Tensor x, torch::Tensor w, torch::Tensor out,
@@ -31,7 +31,7 @@ void rope_append_f32(torch::Tensor src, c10::optional<torch::Tensor> bias,
                      torch::Tensor cos_table, torch::Tensor sin_table,
                      c10::optional<torch::Tensor> kscale,
                      c10::optional<torch::Tensor> vscale,
-                     c10::optional<torch::Tensor> wpos);
+                     c10::optional<torch::Tensor> wpos, int64_t splits);
 void rope_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                  torch::Tensor kcache, torch::Tensor vcache, torch::Tensor pos,
                  torch::Tensor cos_table, torch::Tensor sin_table,
@@ -39,7 +39,8 @@ void rope_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                  c10::optional<torch::Tensor> vscale,
                  c10::optional<torch::Tensor> wpos);
 void swiglu(torch::Tensor gu, torch::Tensor y);
-void swiglu_f32(torch::Tensor gu_f32, torch::Tensor y, int64_t N);
+void swiglu_f32(torch::Tensor gu_f32, torch::Tensor y, int64_t N,
+                int64_t splits);
 void dequant_int8(torch::Tensor w, torch::Tensor scales, torch::Tensor out,
                   int64_t group, bool packed);
 void dequant_int4(torch::Tensor w, torch::Tensor scales, torch::Tensor out,
@@ -47,12 +48,12 @@ void dequant_int4(torch::Tensor w, torch::Tensor scales, torch::Tensor out,
 void dequant_mxfp4(torch::Tensor w, torch::Tensor scales, torch::Tensor out);
 void set_splitk_exact(bool on);
 bool gemm_m16_will_defer(int64_t M, int64_t N, int64_t K, int64_t group,
-                         int64_t bits, int64_t scratch_elems);
-bool gemm_m16(torch::Tensor x, torch::Tensor w,
-              c10::optional<torch::Tensor> scales,
-              c10::optional<torch::Tensor> bias, torch::Tensor out,
-              c10::optional<torch::Tensor> scratch, int64_t group, bool packed,
-              int64_t bits, bool defer_combine);
+                         int64_t bits, int64_t partial_elems);
+int64_t gemm_m16(torch::Tensor x, torch::Tensor w,
+                 c10::optional<torch::Tensor> scales,
+                 c10::optional<torch::Tensor> bias, torch::Tensor out,
+                 c10::optional<torch::Tensor> partials, int64_t group,
+                 bool packed, int64_t bits, bool defer_combine);
 void moe_gateup(torch::Tensor x, torch::Tensor w,
                 c10::optional<torch::Tensor> scales,
                 c10::optional<torch::Tensor> bias, torch::Tensor we,
@@ -110,19 +111,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "order-independent (grid-rounded) split-k partial sums on/off");
   m.def("gemm_m16_will_defer", &dnet::gemm_m16_will_defer,
         "would gemm_m16(defer_combine=true) defer for this shape");
+  // The *_f32 consumers sum `splits` slices of the split-k partials and
+  // write nothing back. splits = 1 (the default) is the legacy calling
+  // convention: one f32 buffer, read and re-zeroed.
   m.def("rope_append_f32", &dnet::rope_append_f32,
-        "RoPE+append reading+re-zeroing the qkv split-k f32 scratch");
+        "RoPE+append summing the qkv split-k f32 partial slices",
+        py::arg("src"), py::arg("bias"), py::arg("qout"), py::arg("Hkv"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("pos"),
+        py::arg("cos_table"), py::arg("sin_table"), py::arg("kscale"),
+        py::arg("vscale"), py::arg("wpos"), py::arg("splits") = 1);
   m.def("resid_add_f32", &dnet::resid_add_f32,
-        "h += split-k f32 scratch (re-zeroed)");
+        "h += sum of the split-k f32 partial slices", py::arg("h"),
+        py::arg("xf"), py::arg("splits") = 1);
   m.def("rmsnorm_f32", &dnet::rmsnorm_f32,
-        "RMSNorm+residual reading+re-zeroing the split-k f32 scratch");
+        "RMSNorm+residual summing the split-k f32 partial slices",
+        py::arg("xf"), py::arg("residual"), py::arg("w"), py::arg("y"),
+        py::arg("eps"), py::arg("splits") = 1);
   m.def("swiglu_f32", &dnet::swiglu_f32,
-        "SwiGLU reading+re-zeroing the split-k f32 scratch");
+        "SwiGLU summing the split-k f32 partial slices", py::arg("gu_f32"),
+        py::arg("y"), py::arg("N"), py::arg("splits") = 1);
   m.def("dequant_int8", &dnet::dequant_int8, "grouped-int8 -> bf16 dequant");
   m.def("dequant_int4", &dnet::dequant_int4, "packed-int4 -> bf16 dequant");
   m.def("gemm_m16", &dnet::gemm_m16, "MFMA decode GEMM (M<=16, bf16 or int8)",
         py::arg("x"), py::arg("w"), py::arg("scales"), py::arg("bias"),
-        py::arg("out"), py::arg("scratch"), py::arg("group"),
+        py::arg("out"), py::arg("partials"), py::arg("group"),
         py::arg("packed"), py::arg("bits"),
         py::arg("defer_combine") = false);
   m.def("moe_gateup", &dnet::moe_gateup,

@@ -78,6 +78,72 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
   return r;
 }
 
+// Split-k partials of the decode GEMM: `splits` slices of `stride` f32 each
+// (layout [sk][M][N], gemm_m16.hip.cpp). The consumers sum slices
+// 0..splits-1 in that fixed order, in f32, so the result does not depend
+// on which split finished first.
+__device__ __forceinline__ float sum_slices(const float* p,
+                                            const int64_t stride,
+                                            const int splits) {
+  float v = p[0];
+  for (int s = 1; s < splits; ++s) v += p[s * stride];
+  return v;
+}
+
+__device__ __forceinline__ void slice_add(float& a, const float b) { a += b; }
+__device__ __forceinline__ void slice_add(float4& a, const float4 b) {
+  a.x += b.x;
+  a.y += b.y;
+  a.z += b.z;
+  a.w += b.w;
+}
+
+// out[k] = sum over the slices, in order, of the T (float or float4) at
+// p[k], for NP places at once. All SK * NP loads are issued before the
+// first add: with a run-time trip count each load waits for the add
+// before it, and a consumer that reads 8 slices pays 8 memory latencies
+// in a row (measured: rmsnorm 13.1 us against 5.8 us for one slice).
+template <typename T, int NP, int SK>
+__device__ __forceinline__ void sum_slices_fixed(const float* const (&p)[NP],
+                                                 const int64_t stride,
+                                                 T (&out)[NP]) {
+  T t[SK][NP];
+#pragma unroll
+  for (int s = 0; s < SK; ++s)
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      t[s][k] = *reinterpret_cast<const T*>(p[k] + s * stride);
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    out[k] = t[0][k];
+#pragma unroll
+    for (int s = 1; s < SK; ++s) slice_add(out[k], t[s][k]);
+  }
+}
+
+// The split counts pick_splitk produces are powers of two; anything else
+// (a forced count) takes the loop.
+template <typename T, int NP>
+__device__ __forceinline__ void sum_slices_multi(const float* const (&p)[NP],
+                                                 const int64_t stride,
+                                                 const int splits,
+                                                 T (&out)[NP]) {
+  switch (splits) {  // uniform over the grid
+    case 1: sum_slices_fixed<T, NP, 1>(p, stride, out); break;
+    case 2: sum_slices_fixed<T, NP, 2>(p, stride, out); break;
+    case 4: sum_slices_fixed<T, NP, 4>(p, stride, out); break;
+    case 8: sum_slices_fixed<T, NP, 8>(p, stride, out); break;
+    case 16: sum_slices_fixed<T, NP, 16>(p, stride, out); break;
+    default:
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        out[k] = *reinterpret_cast<const T*>(p[k]);
+        for (int s = 1; s < splits; ++s)
+          slice_add(out[k], *reinterpret_cast<const T*>(p[k] + s * stride));
+      }
+  }
+}
+
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // The torch-ROCm stream for the current device (what torch kernels launch on).

@@ -16,7 +16,11 @@
 // HBM bursts).
 //
 // Wave tile: 16 N-columns; block = 4 waves = 64 columns; gridDim.y = SPLITK
-// K-splits (partials combined by f32 atomics + a convert/bias kernel).
+// K-splits. Split s stores its whole [M,N] f32 tile with plain stores into
+// slice s of a partials buffer laid out [sk][M][N]; whoever reads the
+// result (the convert/bias kernel, or the fused rope / rmsnorm / resid-add
+// / swiglu consumers) sums slices 0..sk-1 in that fixed order. No atomics,
+// nothing to zero beforehand, and two launches give the same bits.
 #include "common.h"
 
 namespace dnet {
@@ -44,13 +48,14 @@ __device__ __forceinline__ bf16x8 deq4(const uint8_t* qb, const float s) {
 }
 
 // Opt-in reproducible split-k (set_splitk_exact, OFF by default; the
-// default path adds the raw f32 partials). When on, every partial is
-// rounded to a fixed 2^-16 grid before the f32 atomic. Sums of grid values
+// default path stores the raw f32 partials). When on, every partial is
+// rounded to a fixed 2^-16 grid before it is stored. Sums of grid values
 // stay exactly representable in f32 while their magnitude is below 2^8, so
 // the additions are exact and the total does not depend on the order in
-// which the splits arrive (plain f32 atomics at sk >= 4 give a different
-// last bit per run, and 64 layers + greedy sampling turn that into
-// different tokens). The price is an absolute precision floor: each
+// which the partials are added. The slices are summed in a fixed order, so
+// the default path is run-to-run reproducible too; this mode additionally
+// keeps the bits of builds that combined the splits in arrival order
+// (f32 atomics). The price is an absolute precision floor: each
 // partial carries up to 2^-17 of rounding error and one below 2^-17 is
 // flushed to zero, so the mode is meant for O(1) activations (synthetic
 // benchmark runs), not for general use. Sums beyond 2^8 are still correct
@@ -237,8 +242,10 @@ __global__ void gemm_m16_kernel(const short* __restrict__ x,
       const int m = t * 16 + (lane >> 4) * 4 + r;
       if (m >= M) continue;
       if (splitk > 1) {
-        atomicAdd(out_f32 + (int64_t)m * N + n,
-                  exact ? splitk_grid(a2[r]) : a2[r]);
+        // split s owns slice s of the [sk][M][N] partials: a plain store,
+        // zeros included when this split had no k of its own
+        out_f32[((int64_t)blockIdx.y * M + m) * N + n] =
+            exact ? splitk_grid(a2[r]) : a2[r];
       } else {
         float v = a2[r];
         if (bias != nullptr) v += bits2f(bias[n]);
@@ -573,8 +580,10 @@ __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
       const int m = t * 16 + (lane >> 4) * 4 + r;
       if (m >= M) continue;
       if (splitk > 1) {
-        atomicAdd(out_f32 + (int64_t)m * N + n,
-                  exact ? splitk_grid(a2[r]) : a2[r]);
+        // split s owns slice s of the [sk][M][N] partials: a plain store,
+        // zeros included when this split had no k of its own
+        out_f32[((int64_t)blockIdx.y * M + m) * N + n] =
+            exact ? splitk_grid(a2[r]) : a2[r];
       } else {
         float v = a2[r];
         if (bias != nullptr) v += bits2f(bias[n]);
@@ -587,28 +596,24 @@ __global__ __launch_bounds__(256, MINW) void gemm_m16_stream_kernel(
 __global__ void f32_to_bf16_bias_kernel(const float* __restrict__ in,
                                         const short* __restrict__ bias,
                                         short* __restrict__ out,
-                                        const int64_t total, const int N) {
+                                        const int64_t total, const int N,
+                                        const int splits) {
+  // in: [splits][total] partial slices, summed in slice order; read only
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
-    float v = in[i];
+    float v = sum_slices(in + i, total, splits);
     if (bias != nullptr) v += bits2f(bias[i % N]);
     out[i] = f2bits(v);
   }
 }
-
-// One device per process (shard design): number of leading scratch
-// elements holding un-zeroed partials from plain (non-deferred)
-// combines. A bool is NOT enough: a small GEMM's memset after a big
-// combine would clear the flag while stale partials remain beyond its
-// own M*N region and corrupt the next bigger user.
-static int64_t g_scratch_dirty_elems = 0;
 
 // reproducible split-k (see splitk_grid); process-wide, read at launch —
 // set it before graphs are captured
 static bool g_splitk_exact = false;
 void set_splitk_exact(bool on) { g_splitk_exact = on; }
 
-static int pick_splitk(int64_t N, int64_t K, int64_t M, int64_t scratch_elems,
+// partial_elems: capacity of the [sk][M][N] partials buffer in f32.
+static int pick_splitk(int64_t N, int64_t K, int64_t M, int64_t partial_elems,
                        int min_pairs, int g_align) {
   // Target ~1024 blocks (~4 blocks / 16 waves per CU) so HBM latency is
   // covered by wave overlap; each split keeps >= 8 K-chunk-pairs of work.
@@ -617,8 +622,12 @@ static int pick_splitk(int64_t N, int64_t K, int64_t M, int64_t scratch_elems,
     return e ? atoi(e) : 0;
   }();
   const int blocks = (int)((N + 63) / 64);
-  if (forced > 0)
-    return (M * N > scratch_elems || (K / 64) < forced) ? 1 : forced;
+  if (forced > 0) {
+    // every split needs a slice of its own: fall back to a shallower split
+    int sk = (K / 64) < forced ? 1 : forced;
+    while (sk > 1 && sk * M * N > partial_elems) sk /= 2;
+    return sk;
+  }
   int sk = 1;
   while (sk < 32 && blocks * sk < 1024 &&
          (K / 64) / (sk * 2) >= min_pairs &&
@@ -638,22 +647,27 @@ static int pick_splitk(int64_t N, int64_t K, int64_t M, int64_t scratch_elems,
         blocks * (sk / 2) >= 440)
       sk /= 2;
   }
-  if (sk > 1 && M * N > scratch_elems) sk = 1;
+  // one [M,N] slice per split (a doubled span stays G-aligned). The loop
+  // above ends with blocks * sk < 2048, so sk * N < 131072 and 64 rows
+  // need fewer than 8.4 M elements.
+  while (sk > 1 && sk * M * N > partial_elems) sk /= 2;
   return sk;
 }
 
-static bool launch_m16(torch::Tensor x, torch::Tensor w,
-                       c10::optional<torch::Tensor> scales,
-                       c10::optional<torch::Tensor> bias, torch::Tensor out,
-                       c10::optional<torch::Tensor> scratch, int group,
-                       int64_t m0, int M, int bits, bool defer_combine) {
+// Returns the number of splits left un-combined in the partials buffer
+// (the caller's next kernel sums them), or 0 when `out` holds the result.
+static int launch_m16(torch::Tensor x, torch::Tensor w,
+                      c10::optional<torch::Tensor> scales,
+                      c10::optional<torch::Tensor> bias, torch::Tensor out,
+                      c10::optional<torch::Tensor> partials, int group,
+                      int64_t m0, int M, int bits, bool defer_combine) {
   const int64_t K = x.size(1), N = w.size(0);
   auto stream = current_stream();
-  const int64_t scratch_elems = scratch.has_value() ? scratch->numel() : 0;
+  const int64_t partial_elems = partials.has_value() ? partials->numel() : 0;
   // the streamed schedule tolerates short splits (one combined round
   // trip per 4-pair tile), so quantized paths split deeper to fill the
   // 256 CUs on small-N shapes (qkv/o run at <2 blocks/CU otherwise)
-  const int sk = pick_splitk(N, K, M, scratch_elems, bits < 16 ? 4 : 8,
+  const int sk = pick_splitk(N, K, M, partial_elems, bits < 16 ? 4 : 8,
                              bits < 16 ? std::max<int>((int)group, 64) : 64);
   const short* bptr = bias.has_value() ? (const short*)bias->data_ptr() : nullptr;
   const dim3 grid((unsigned)((N + 63) / 64), sk);
@@ -662,23 +676,12 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
   short* op = (short*)out.data_ptr() + m0 * N;
   float* fp = nullptr;
   if (sk > 1) {
-    TORCH_CHECK(scratch.has_value() && scratch->numel() >= (int64_t)M * N,
-                "split-k scratch required");
-    fp = (float*)scratch->data_ptr();
-    // The scratch must be zero before the atomics. Deferred-combine
-    // consumers (rope/swiglu/rmsnorm f32 variants) re-zero what they
-    // read, so a chain of deferred GEMMs never needs a memset; the
-    // plain combine does NOT re-zero — a combine-side in[i]=0 write
-    // measured a 3.5x MoE decode slowdown (the grouped expert kernels
-    // dropped ~3.9 -> ~2.5 TB/s whenever the combine left dirtied
-    // scratch lines behind; bisected to that single change) — so the
-    // NEXT split-k launch after a combine memsets first.
-    if (g_scratch_dirty_elems > 0) {
-      const int64_t span = std::max<int64_t>(g_scratch_dirty_elems,
-                                             (int64_t)M * N);
-      DNET_CHECK_HIP(hipMemsetAsync(fp, 0, sizeof(float) * span, stream));
-      g_scratch_dirty_elems = 0;
-    }
+    // Every split stores its whole [M,N] slice, so the buffer needs no
+    // zeroing before the launch and nobody has to clean up after it.
+    TORCH_CHECK(partials.has_value() &&
+                    partials->numel() >= (int64_t)sk * M * N,
+                "split-k partials buffer required");
+    fp = (float*)partials->data_ptr();
   }
   const short* sp = bits < 16 ? (const short*)scales->data_ptr() : nullptr;
   const short* bp1 = sk > 1 ? nullptr : bptr;
@@ -744,35 +747,36 @@ static bool launch_m16(torch::Tensor x, torch::Tensor w,
 #undef LAUNCH_STREAM_G8
 #undef LAUNCH_STREAM_G4
   if (sk > 1) {
-    // defer_combine: the caller's next kernel reads (and re-zeroes) the
-    // f32 scratch itself — skip the convert/bias pass
-    if (defer_combine && bptr == nullptr) return true;
+    // defer_combine: the caller's next kernel sums the f32 slices itself
+    // — skip the convert/bias pass
+    if (defer_combine && bptr == nullptr) return sk;
     const int64_t total = (int64_t)M * N;
     const int cgrid = (int)std::min<int64_t>((total + 255) / 256, 2048);
     hipLaunchKernelGGL(f32_to_bf16_bias_kernel, dim3(cgrid), dim3(256), 0,
-                       stream, fp, bptr, op, total, (int)N);
-    g_scratch_dirty_elems =
-        std::max<int64_t>(g_scratch_dirty_elems, (int64_t)M * N);
+                       stream, fp, bptr, op, total, (int)N, sk);
   }
-  return false;
+  return 0;
 }
 
 // Would gemm_m16(defer_combine=true) actually defer for this shape?
 // (Pure: lets callers decide between the fused-consumer and the
 // bias-in-combine paths BEFORE launching.)
 bool gemm_m16_will_defer(int64_t M, int64_t N, int64_t K, int64_t group,
-                         int64_t bits, int64_t scratch_elems) {
+                         int64_t bits, int64_t partial_elems) {
   if (M > 64 || M <= 2) return false;
-  const int sk = pick_splitk(N, K, M, scratch_elems, bits < 16 ? 4 : 8,
+  const int sk = pick_splitk(N, K, M, partial_elems, bits < 16 ? 4 : 8,
                              bits < 16 ? std::max<int>((int)group, 64) : 64);
   return sk > 1;
 }
 
-bool gemm_m16(torch::Tensor x, torch::Tensor w,
-              c10::optional<torch::Tensor> scales,
-              c10::optional<torch::Tensor> bias, torch::Tensor out,
-              c10::optional<torch::Tensor> scratch, int64_t group,
-              bool packed, int64_t bits, bool defer_combine) {
+// Returns 0 when `out` holds the result, else the number of split-k
+// slices the deferred result occupies in `partials` ([sk][M][N] f32): the
+// caller hands that count to the consumer kernel.
+int64_t gemm_m16(torch::Tensor x, torch::Tensor w,
+                 c10::optional<torch::Tensor> scales,
+                 c10::optional<torch::Tensor> bias, torch::Tensor out,
+                 c10::optional<torch::Tensor> partials, int64_t group,
+                 bool packed, int64_t bits, bool defer_combine) {
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   DNET_CHECK(K % 64 == 0, "K % 64 == 0 required for the MFMA path");
   DNET_CHECK(out.size(0) == M && out.size(1) == N, "shape");
@@ -792,11 +796,11 @@ bool gemm_m16(torch::Tensor x, torch::Tensor w,
   // defer only meaningful for the single-chunk (M <= 64) decode path:
   // multiple chunks could pick different sk and leave a mixed state
   const bool defer = defer_combine && M <= 64 && !bias.has_value();
-  bool deferred = false;
+  int64_t deferred = 0;
   int64_t m0 = 0;
   while (m0 < M) {
     const int mt = (int)std::min<int64_t>(M - m0, 64);
-    deferred = launch_m16(x, w, scales, bias, out, scratch, (int)group, m0,
+    deferred = launch_m16(x, w, scales, bias, out, partials, (int)group, m0,
                           mt, (int)bits, defer);
     m0 += mt;
   }

@@ -16,11 +16,13 @@ namespace dnet {
 // Q8: KV cache stored int8 with one bf16 scale per 64-dim group
 // (reference: utils/model.py make_cache kv quantization, 8-bit group 64).
 // F32: split-k-fused variant — q/k/v come from the UN-COMBINED f32
-// split-k scratch of the qkv GEMM (layout [B, (Hq+2*Hkv)*D], row stride
-// ldq), bias (bf16, optional) is applied here, the rotated q goes to a
-// dedicated bf16 buffer `qout`, and every scratch element read is
-// re-zeroed for the next split-k use. Removes the f32->bf16 combine
-// kernel from the decode dependency chain.
+// split-k partials of the qkv GEMM (`splits` slices of [B, (Hq+2*Hkv)*D],
+// row stride ldq, summed here in slice order and only read), bias (bf16,
+// optional) is applied here and the rotated q goes to a dedicated bf16
+// buffer `qout`. Removes the f32->bf16 combine kernel from the decode
+// dependency chain. splits == 1 is the one legacy mode, kept for callers
+// that fill a single [B, N] f32 buffer themselves with the positional
+// signature that has no split count: every element read is re-zeroed.
 template <bool Q8, bool F32 = false>
 __global__ void rope_append_kernel(short* __restrict__ q,
                                    short* __restrict__ k,
@@ -38,7 +40,8 @@ __global__ void rope_append_kernel(short* __restrict__ q,
                                    const int ldv,
                                    float* __restrict__ src = nullptr,
                                    const short* __restrict__ biasv = nullptr,
-                                   short* __restrict__ qout = nullptr) {
+                                   short* __restrict__ qout = nullptr,
+                                   const int splits = 1) {
   const int b = blockIdx.x;
   const int h = blockIdx.y;
   const int i = threadIdx.x;  // 0 .. max(D/2,64)-1; lanes >= D/2 idle
@@ -47,17 +50,23 @@ __global__ void rope_append_kernel(short* __restrict__ q,
   const bool act = i < half;
   const float c = act ? cost[(int64_t)p * half + i] : 0.f;
   const float s = act ? sint[(int64_t)p * half + i] : 0.f;
+  const int64_t slice = (int64_t)gridDim.x * ldq;  // F32: [B, ldq] per split
   if (h < Hq) {
     if (!act) return;
     if (F32) {
       float* row = src + (int64_t)b * ldq + h * D;
-      float x1 = row[i], x2 = row[i + half];
+      const float* const src2[2] = {row + i, row + i + half};
+      float xs[2];
+      sum_slices_multi<float, 2>(src2, slice, splits, xs);
+      float x1 = xs[0], x2 = xs[1];
       if (biasv != nullptr) {
         x1 += bits2f(biasv[h * D + i]);
         x2 += bits2f(biasv[h * D + i + half]);
       }
-      row[i] = 0.f;
-      row[i + half] = 0.f;
+      if (splits == 1) {
+        row[i] = 0.f;
+        row[i + half] = 0.f;
+      }
       short* qrow = qout + (int64_t)b * Hq * D + h * D;
       qrow[i] = f2bits(x1 * c - x2 * s);
       qrow[i + half] = f2bits(x2 * c + x1 * s);
@@ -76,19 +85,25 @@ __global__ void rope_append_kernel(short* __restrict__ q,
     const int kcol = (Hq + hk) * D, vcol = (Hq + Hkv + hk) * D;
     float* krowf = src + (int64_t)b * ldq + kcol;
     float* vrowf = src + (int64_t)b * ldq + vcol;
-    float x1 = krowf[i], x2 = krowf[i + half];
-    v1 = vrowf[i];
-    v2 = vrowf[i + half];
+    const float* const src4[4] = {krowf + i, krowf + i + half, vrowf + i,
+                                  vrowf + i + half};
+    float xs[4];
+    sum_slices_multi<float, 4>(src4, slice, splits, xs);
+    float x1 = xs[0], x2 = xs[1];
+    v1 = xs[2];
+    v2 = xs[3];
     if (biasv != nullptr) {
       x1 += bits2f(biasv[kcol + i]);
       x2 += bits2f(biasv[kcol + i + half]);
       v1 += bits2f(biasv[vcol + i]);
       v2 += bits2f(biasv[vcol + i + half]);
     }
-    krowf[i] = 0.f;
-    krowf[i + half] = 0.f;
-    vrowf[i] = 0.f;
-    vrowf[i + half] = 0.f;
+    if (splits == 1) {
+      krowf[i] = 0.f;
+      krowf[i + half] = 0.f;
+      vrowf[i] = 0.f;
+      vrowf[i + half] = 0.f;
+    }
     k1 = x1 * c - x2 * s;
     k2 = x2 * c + x1 * s;
   } else if (act) {
@@ -159,21 +174,23 @@ __global__ void rope_append_kernel(short* __restrict__ q,
   }
 }
 
-// Fused qkv-split-k-combine + RoPE + append: src = f32 scratch of the
-// qkv GEMM (un-combined), qout receives the rotated+biased q rows.
+// Fused qkv-split-k-combine + RoPE + append: src = the `splits` f32
+// partial slices of the qkv GEMM (un-combined), qout receives the
+// rotated+biased q rows.
 void rope_append_f32(torch::Tensor src, c10::optional<torch::Tensor> bias,
                      torch::Tensor qout, int64_t Hkv, torch::Tensor kcache,
                      torch::Tensor vcache, torch::Tensor pos,
                      torch::Tensor cos_table, torch::Tensor sin_table,
                      c10::optional<torch::Tensor> kscale,
                      c10::optional<torch::Tensor> vscale,
-                     c10::optional<torch::Tensor> wpos) {
+                     c10::optional<torch::Tensor> wpos, int64_t splits) {
   const int64_t B = qout.size(0), Hq = qout.size(1), D = qout.size(2);
   const int64_t Smax = kcache.size(2);
   const int64_t N = (Hq + 2 * Hkv) * D;
   DNET_CHECK(D % 2 == 0 && D / 2 <= 1024, "head_dim");
   DNET_CHECK(qout.is_contiguous() && src.is_contiguous(), "contig");
-  DNET_CHECK(src.numel() >= B * N, "scratch too small");
+  DNET_CHECK(splits >= 1 && src.numel() >= splits * B * N,
+             "partials too small");
   DNET_CHECK(cos_table.dtype() == torch::kFloat32, "cos table f32");
   auto stream = current_stream();
   const bool q8 = kcache.dtype() == torch::kInt8;
@@ -191,7 +208,8 @@ void rope_append_f32(torch::Tensor src, c10::optional<torch::Tensor> bias,
                        (const float*)cos_table.data_ptr(),
                        (const float*)sin_table.data_ptr(), (int)Hq, (int)Hkv,
                        (int)Smax, (int)D, (int)N, 0, 0,
-                       (float*)src.data_ptr(), bp, (short*)qout.data_ptr());
+                       (float*)src.data_ptr(), bp, (short*)qout.data_ptr(),
+                       (int)splits);
   else
     hipLaunchKernelGGL((rope_append_kernel<false, true>),
                        dim3((unsigned)B, (unsigned)(Hq + Hkv)), dim3(thr), 0,
@@ -201,7 +219,8 @@ void rope_append_f32(torch::Tensor src, c10::optional<torch::Tensor> bias,
                        (const float*)cos_table.data_ptr(),
                        (const float*)sin_table.data_ptr(), (int)Hq, (int)Hkv,
                        (int)Smax, (int)D, (int)N, 0, 0,
-                       (float*)src.data_ptr(), bp, (short*)qout.data_ptr());
+                       (float*)src.data_ptr(), bp, (short*)qout.data_ptr(),
+                       (int)splits);
 }
 
 void rope_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,

@@ -30,24 +30,29 @@ __global__ void swiglu_kernel(const short* __restrict__ gu,
   }
 }
 
-// Split-k-fused variant: reads the UN-COMBINED f32 split-k scratch of
-// the gate/up GEMM directly (bias-free), re-zeroing it for the next
-// split-k use — removes the f32->bf16 combine kernel from the decode
-// dependency chain (each ~5 us launch-bound hop, 64 per step).
+// Split-k-fused variant: sums the `splits` UN-COMBINED f32 split-k slices
+// of the gate/up GEMM (layout [splits][T][2I], bias-free) in slice order
+// and only reads them — removes the f32->bf16 combine kernel from the
+// decode dependency chain (each ~5 us launch-bound hop, 64 per step).
+// splits == 1 is the legacy mode: one [T,2I] buffer, read and re-zeroed.
 __global__ void swiglu_f32_kernel(float* __restrict__ gu,
                                   short* __restrict__ y, const int64_t I,
-                                  const int64_t T) {
+                                  const int64_t T, const int splits) {
   const int64_t nvec = T * I / 4;
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
        idx < nvec; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t row = idx / (I / 4);
     const int64_t col = idx % (I / 4);
-    float4 g = reinterpret_cast<float4*>(gu + row * 2 * I)[col];
-    float4 u = reinterpret_cast<float4*>(gu + row * 2 * I + I)[col];
-    reinterpret_cast<float4*>(gu + row * 2 * I)[col] =
-        make_float4(0.f, 0.f, 0.f, 0.f);
-    reinterpret_cast<float4*>(gu + row * 2 * I + I)[col] =
-        make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t slice = T * 2 * I;
+    float* gp = gu + row * 2 * I + col * 4;
+    const float* const src2[2] = {gp, gp + I};
+    float4 gusum[2];
+    sum_slices_multi<float4, 2>(src2, slice, splits, gusum);
+    const float4 g = gusum[0], u = gusum[1];
+    if (splits == 1) {
+      *reinterpret_cast<float4*>(gp) = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(gp + I) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     short4v o;
     const float gf[4] = {g.x, g.y, g.z, g.w};
     const float uf[4] = {u.x, u.y, u.z, u.w};
@@ -60,18 +65,21 @@ __global__ void swiglu_f32_kernel(float* __restrict__ gu,
   }
 }
 
-void swiglu_f32(torch::Tensor gu_f32, torch::Tensor y, int64_t N) {
+void swiglu_f32(torch::Tensor gu_f32, torch::Tensor y, int64_t N,
+                int64_t splits) {
   const int64_t I = y.size(-1);
   const int64_t T = y.numel() / I;
   DNET_CHECK(N == 2 * I, "gu width must be 2*I");
   DNET_CHECK(I % 4 == 0, "I % 4");
-  DNET_CHECK(gu_f32.numel() >= T * N, "scratch too small");
+  DNET_CHECK(splits >= 1 && gu_f32.numel() >= splits * T * N,
+             "partials too small");
   DNET_CHECK(gu_f32.is_contiguous() && y.is_contiguous(), "contig");
   auto stream = current_stream();
   const int64_t nvec = T * I / 4;
   const int grid = (int)std::min<int64_t>((nvec + 255) / 256, 2048);
   hipLaunchKernelGGL(swiglu_f32_kernel, dim3(grid), dim3(256), 0, stream,
-                     (float*)gu_f32.data_ptr(), (short*)y.data_ptr(), I, T);
+                     (float*)gu_f32.data_ptr(), (short*)y.data_ptr(), I, T,
+                     (int)splits);
 }
 
 void swiglu(torch::Tensor gu, torch::Tensor y) {

@@ -38,12 +38,38 @@ def main():
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=str, default="1,16,32,64")
+    ap.add_argument("--shapes", type=str, default="",
+                    help="comma-separated shape names (default: all)")
+    ap.add_argument("--packed-only", action="store_true",
+                    help="time only the packed int8 and int4 MFMA paths "
+                         "(no scalar GEMV, no bf16)")
     args = ap.parse_args()
     ms = [int(v) for v in args.m.split(",")]
     dev = "cuda:0"
     nat = _native()
+    want = [v for v in args.shapes.split(",") if v]
     for name, N, K in SHAPES:
+        if want and name not in want:
+            continue
         wf = torch.randn(N, K, dtype=torch.bfloat16, device=dev) / 30
+        if args.packed_only:
+            q, scales = ops.quantize_int8(wf, 128)
+            qp = ops.pack_int8_mfma(q)
+            q4, s4 = ops.quantize_int4(wf, 128)
+            q4p = ops.pack_int4_mfma(q4)
+            scratch = ops._get_partials(dev)
+            for M in ms:
+                x = torch.randn(M, K, dtype=torch.bfloat16, device=dev)
+                out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+                t8 = bench(lambda: nat.gemm_m16(x, qp, scales, None, out,
+                                                scratch, 128, True, 8), 200)
+                t4 = bench(lambda: nat.gemm_m16(x, q4p, s4, None, out,
+                                                scratch, 128, True, 4), 200)
+                print(f"{name:8s} N={N:6d} K={K:6d} M={M:2d}  "
+                      f"i8-packed {t8*1e6:7.1f}us | i4-packed {t4*1e6:7.1f}us")
+            del wf, q, scales, qp, q4, s4, q4p
+            torch.cuda.empty_cache()
+            continue
         q, scales = ops.quantize_int8(wf, 128)
         qp = ops.pack_int8_mfma(q)
         wbytes_i8 = q.numel() + scales.numel() * 2
@@ -51,7 +77,7 @@ def main():
         for M in ms:
             x = torch.randn(M, K, dtype=torch.bfloat16, device=dev)
             out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-            scratch = ops._get_scratch(dev)
+            scratch = ops._get_partials(dev)
 
             t_pk = bench(lambda: nat.gemm_m16(x, qp, scales, None, out,
                                               scratch, 128, True, 8))
