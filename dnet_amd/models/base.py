@@ -861,6 +861,14 @@ class RingModel:
         positions = torch.arange(p0, p0 + T, device=h.device)
         layer_ids = list(layer_ids)
         dq_ev = self._dequant_prefetch(layer_ids, -1)  # prefetch layer 0
+        # in-place path: fused RoPE+append of the chunk's rows, then flash
+        # attention straight off the (bf16 or int8) cache. No torch rope,
+        # no slot dequant, no K/V/q/out copies. DNET_PREFILL_INPLACE=0
+        # keeps the unfused path below.
+        inplace = (self.cp_size == 1 and h.is_cuda
+                   and h.dtype == torch.bfloat16 and ops.has_native()
+                   and ops.attn_prefill_kv_supported(d, d, kv.quantized)
+                   and os.environ.get("DNET_PREFILL_INPLACE", "1") != "0")
         for i, lid in enumerate(layer_ids):
             lw = self._layer(lid)
             if dq_ev is not None:
@@ -877,6 +885,20 @@ class RingModel:
                                 c.rms_eps).view(B, T, nq, d)
                 k = ops.rmsnorm(k.reshape(-1, d).contiguous(), None, lw.k_norm,
                                 c.rms_eps).view(B, T, nkv, d)
+            if inplace:
+                li = kv.local[lid]
+                window, sinks = self._attn_params(lid, lw)
+                ks = kv.kscale[li] if kv.quantized else None
+                vs = kv.vscale[li] if kv.quantized else None
+                qr = ops.rope_append_rows(q, k, v, kv.k[li], kv.v[li], p0,
+                                          self.cos, self.sin, ks, vs)
+                attn = ops.attn_prefill_kv(qr, kv.k[li], kv.v[li], p0 + T,
+                                           d ** -0.5, p0, window, sinks,
+                                           ks, vs)
+                o = self._tp_reduce(lw.o(attn.view(B * T, nq * d)))
+                y2 = ops.rmsnorm(o, flat, lw.mlp_norm, c.rms_eps)
+                flat.add_(self._tp_reduce(self._mlp(y2, lw)))
+                continue
             q = ops.rope_apply(q, self.cos, self.sin, positions)
             k = ops.rope_apply(k, self.cos, self.sin, positions)
             li = kv.local[lid]

@@ -236,6 +236,61 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return out
 
 
+_PREFILL_KV_DIMS = {(128, 128), (64, 64), (96, 96)}
+
+
+def attn_prefill_kv_supported(d: int, dv: int, int8: bool) -> bool:
+    """Head dims the in-place prefill pair (rope_append_rows +
+    attn_prefill_kv) serves; an int8 cache needs whole 64-dim groups."""
+    return (d, dv) in _PREFILL_KV_DIMS and not (int8 and d % 64)
+
+
+def rope_append_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                     kcache: torch.Tensor, vcache: torch.Tensor, p0: int,
+                     cos: torch.Tensor, sin: torch.Tensor,
+                     kscale: torch.Tensor | None = None,
+                     vscale: torch.Tensor | None = None) -> torch.Tensor:
+    """Fused prefill RoPE + KV append. q [B,T,Hq,D], k/v [B,T,Hkv,D] bf16
+    (column slices of the fused qkv buffer are fine: head stride D, any
+    token/batch stride); token t sits at position p0+t. Rotated k and raw
+    v go to rows [p0, p0+T) of kcache/vcache [B,Hkv,Smax,D] (bf16, or int8
+    with bf16 scales [B,Hkv,Smax,D/64]; any batch stride); no other row is
+    written. Returns the rotated q as [B,Hq,T,D], the layout
+    ``attn_prefill_kv`` reads. Eager only (p0 is a host int)."""
+    if q.is_cuda:
+        B, T, Hq, D = q.shape
+        q_rot = torch.empty(B, Hq, T, D, dtype=q.dtype, device=q.device)
+        _native().rope_append_rows(q, k, v, q_rot, kcache, vcache, int(p0),
+                                   cos, sin, kscale, vscale)
+        return q_rot
+    return ref.rope_append_rows(q, k, v, kcache, vcache, int(p0), cos, sin,
+                                kscale, vscale)
+
+
+def attn_prefill_kv(q: torch.Tensor, kcache: torch.Tensor,
+                    vcache: torch.Tensor, kv_len: int, scale: float,
+                    q_off: int, window: int = 0,
+                    sinks: torch.Tensor | None = None,
+                    kscale: torch.Tensor | None = None,
+                    vscale: torch.Tensor | None = None) -> torch.Tensor:
+    """Flash prefill attention that reads the KV cache in place (bf16 or
+    int8 + scales, strides as ``KVCache.slot()`` hands them out): the
+    semantics of ``attn_prefill`` on ``cache[:, :, :kv_len]`` (rows
+    >= kv_len are never read). q [B,Hq,T,D] contiguous -> [B, T, Hq*Dv],
+    token-major for the o-projection. A query row's output bits do not
+    depend on how the prompt was chunked."""
+    if q.is_cuda:
+        B, Hq, T, _ = q.shape
+        out = torch.empty(B, T, Hq * vcache.shape[-1], dtype=q.dtype,
+                          device=q.device)
+        _native().attn_prefill_kv(q, kcache, vcache, sinks, out, int(kv_len),
+                                  int(q_off), int(window or 0), float(scale),
+                                  kscale, vscale)
+        return out
+    return ref.attn_prefill_kv(q, kcache, vcache, int(kv_len), scale,
+                               int(q_off), window or 0, sinks, kscale, vscale)
+
+
 def rope_append(q, k, v, kcache, vcache, pos, cos, sin,
                 kscale=None, vscale=None, wpos=None) -> None:
     if q.is_cuda:

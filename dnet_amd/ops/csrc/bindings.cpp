@@ -38,6 +38,18 @@ void rope_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                  c10::optional<torch::Tensor> kscale,
                  c10::optional<torch::Tensor> vscale,
                  c10::optional<torch::Tensor> wpos);
+void rope_append_rows(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                      torch::Tensor qout, torch::Tensor kcache,
+                      torch::Tensor vcache, int64_t p0,
+                      torch::Tensor cos_table, torch::Tensor sin_table,
+                      c10::optional<torch::Tensor> kscale,
+                      c10::optional<torch::Tensor> vscale);
+void attn_prefill_kv(torch::Tensor q, torch::Tensor kcache,
+                     torch::Tensor vcache, c10::optional<torch::Tensor> sinks,
+                     torch::Tensor out, int64_t kv_len, int64_t q_off,
+                     int64_t window, double scale,
+                     c10::optional<torch::Tensor> kscale,
+                     c10::optional<torch::Tensor> vscale);
 void swiglu(torch::Tensor gu, torch::Tensor y);
 void swiglu_f32(torch::Tensor gu_f32, torch::Tensor y, int64_t N,
                 int64_t splits);
@@ -106,6 +118,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vcache"), py::arg("pos"), py::arg("cos_table"),
         py::arg("sin_table"), py::arg("kscale"), py::arg("vscale"),
         py::arg("wpos") = c10::nullopt);
+  m.def("rope_append_rows", &dnet::rope_append_rows,
+        "fused prefill RoPE + KV append of T token rows",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("qout"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("p0"),
+        py::arg("cos_table"), py::arg("sin_table"), py::arg("kscale"),
+        py::arg("vscale"));
+  m.def("attn_prefill_kv", &dnet::attn_prefill_kv,
+        "MFMA flash prefill attention reading the bf16/int8 KV cache in place",
+        py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("sinks"),
+        py::arg("out"), py::arg("kv_len"), py::arg("q_off"),
+        py::arg("window"), py::arg("scale"), py::arg("kscale"),
+        py::arg("vscale"));
   m.def("swiglu", &dnet::swiglu, "fused SwiGLU");
   m.def("set_splitk_exact", &dnet::set_splitk_exact,
         "order-independent (grid-rounded) split-k partial sums on/off");

@@ -342,6 +342,62 @@ def rope_append(q, k, v, kcache, vcache, pos, cos, sin,
             vcache[b, :, p] = v[b]
 
 
+def rope_append_rows(q, k, v, kcache, vcache, p0: int, cos, sin,
+                     kscale=None, vscale=None) -> torch.Tensor:
+    """Prefill fused rope+append reference: q [B,T,Hq,D], k/v [B,T,Hkv,D]
+    at positions p0..p0+T-1. Writes rotated k and raw v to cache rows
+    [p0, p0+T) and returns the rotated q as [B,Hq,T,D]. Like the decode
+    append, an int8 cache quantizes the f32 rotation, not its bf16
+    rounding."""
+    T = q.shape[1]
+    positions = torch.arange(p0, p0 + T, device=q.device)
+    q_rot = rope_apply(q, cos, sin, positions).transpose(1, 2).contiguous()
+    kt = rope_apply(k.float(), cos, sin, positions).transpose(1, 2)
+    vt = v.transpose(1, 2)
+    if kcache.dtype == torch.int8:
+        kc, ks = quantize_kv_rows(kt)
+        vc, vs = quantize_kv_rows(vt)
+        kcache[:, :, p0:p0 + T] = kc
+        kscale[:, :, p0:p0 + T] = ks
+        vcache[:, :, p0:p0 + T] = vc
+        vscale[:, :, p0:p0 + T] = vs
+    else:
+        kcache[:, :, p0:p0 + T] = kt.to(kcache.dtype)
+        vcache[:, :, p0:p0 + T] = vt
+    return q_rot
+
+
+def attn_prefill_kv(q, kcache, vcache, kv_len: int, scale: float, q_off: int,
+                    window: int = 0, sinks=None, kscale=None,
+                    vscale=None) -> torch.Tensor:
+    """Causal (+ window, + sinks) prefill attention over cache rows
+    [0, kv_len): q [B,Hq,T,D] -> [B, T, Hq*Dv]. Query t attends
+    s <= q_off+t, s > q_off+t-window, s < kv_len."""
+    B, Hq, T, D = q.shape
+    k, v = kcache[:, :, :kv_len], vcache[:, :, :kv_len]
+    if kcache.dtype == torch.int8:
+        k = dequant_kv(k, kscale[:, :, :kv_len])
+        v = dequant_kv(v, vscale[:, :, :kv_len])
+    Hkv, Dv = k.shape[1], v.shape[-1]
+    G = Hq // Hkv
+    qg = q.float().view(B, Hkv, G, T, D)
+    scores = torch.einsum("bhgtd,bhsd->bhgts", qg, k.float()) * scale
+    pos_q = q_off + torch.arange(T, device=q.device).view(-1, 1)
+    pos_k = torch.arange(kv_len, device=q.device).view(1, -1)
+    mask = pos_k > pos_q
+    if window and window > 0:
+        mask |= pos_k <= pos_q - window
+    scores.masked_fill_(mask, float("-inf"))
+    if sinks is not None:
+        sk = sinks.float().view(1, Hkv, G, 1, 1).expand(B, Hkv, G, T, 1)
+        p = torch.softmax(torch.cat([scores, sk], dim=-1), dim=-1)[..., :-1]
+    else:
+        p = torch.softmax(scores, dim=-1)
+    out = torch.einsum("bhgts,bhsd->bhgtd", p, v.float())
+    return (out.reshape(B, Hq, T, Dv).transpose(1, 2)
+            .reshape(B, T, Hq * Dv).to(q.dtype))
+
+
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     i = gu.shape[-1] // 2
     g = gu[..., :i].float()
