@@ -4,12 +4,15 @@ Reference counterpart: src/dnet/core/models/deepseek_v2.py (mlx_lm wrapper;
 qk_nope + qk_rope split head dims). The MLA projections (q, kv_a with
 shared rope key, kv_a layernorm, kv_b) run through the fused GEMV/GEMM
 linears; decode attention runs on the native flash-decode kernel with the
-MLA head-dim pair (qk 192 / v 128). KV is cached per head (uncompressed
-k/v; latent-cache compression is roadmap). MoE layers use
+MLA head-dim pair (qk 192 / v 128) over the per-head cache, or on the
+latent flash-decode kernel (ops.mla_decode) over the compressed cache.
+MoE layers use
 routed top-k (softmax scoring, greedy) * routed_scaling_factor + shared
 experts; the first ``first_k_dense_replace`` layers are dense.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -346,12 +349,22 @@ class DeepseekV2RingModel(RingModel):
 
     def _latent_attn(self, q_nope, q_pe, kv, li, lw, len_t):
         """Absorbed MQA decode over the latent cache: scores vs the
-        shared [lora+rope] stream, output unfolded per head. Full-smax
-        masked matmuls (hipBLASLt) — graph-capturable, no host syncs."""
+        shared [lora+rope] stream, output unfolded per head. On the GPU
+        the HIP flash-decode kernel (ops.mla_decode) does the attention
+        over the live length; otherwise (CPU, other latent dims,
+        DNET_MLA_KERNEL=0) full-smax masked matmuls. Both are
+        graph-capturable, no host syncs."""
         B = q_nope.shape[0]
+        c = self.cfg
         wk, wv = self._absorbed(lw)
         q_eff = torch.einsum("bhn,hnl->bhl", q_nope, wk)
         ckv, kpe = kv.ckv[li], kv.kpe[li]
+        if (q_eff.is_cuda
+                and ops.mla_decode_supported(c.kv_lora_rank,
+                                             c.qk_rope_head_dim)
+                and os.environ.get("DNET_MLA_KERNEL") != "0"):
+            olat = ops.mla_decode(q_eff, q_pe, ckv, kpe, len_t, self.scale)
+            return torch.einsum("bhl,hvl->bhv", olat, wv)
         scores = (torch.einsum("bhl,bsl->bhs", q_eff, ckv)
                   + torch.einsum("bhr,bsr->bhs", q_pe, kpe)).float()
         scores *= self.scale

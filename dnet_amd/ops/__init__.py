@@ -213,6 +213,49 @@ def attn_decode(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                            kscale, vscale)
 
 
+def mla_decode_supported(lora: int, rope: int) -> bool:
+    """Latent dims the HIP mla_decode kernel serves (every released
+    DeepSeek-V2/V3 checkpoint: kv_lora_rank 512, qk_rope_head_dim 64)."""
+    return (lora, rope) == (512, 64)
+
+
+def _mla_splits(b: int, nh: int, smax: int) -> int:
+    # B x head-tile groups is a handful of blocks (16 for V2-Lite at batch
+    # 16), so split until ~512 blocks (2 per CU: a block holds 73 KB of
+    # LDS) while a split still owns two 64-position chunks of capacity
+    groups = -(-nh // 64)
+    splits = 1
+    while b * groups * splits * 2 <= 512 and splits * 2 <= smax // 128:
+        splits *= 2
+    return splits
+
+
+def mla_decode(q_lat: torch.Tensor, q_pe: torch.Tensor, ckv: torch.Tensor,
+               kpe: torch.Tensor, lens: torch.Tensor, scale: float,
+               splits: int | None = None) -> torch.Tensor:
+    """Absorbed-MLA decode attention over the latent cache.
+
+    q_lat [B,nh,512] (query folded through W_k), q_pe [B,nh,64] (roped),
+    ckv [B,S,512], kpe [B,S,64] bf16 (rows contiguous, any batch stride:
+    ``MLAKVCache`` planes and their ``slot()`` views), lens [B] int32 ->
+    o_lat [B,nh,512] = softmax(scale * (q_lat.ckv^T + q_pe.kpe^T))[:len]
+    @ ckv[:len]. Rows >= len are never read; len 0 gives zeros. ``splits``
+    (split-S factor) defaults to a heuristic over (B, nh, S)."""
+    if q_lat.is_cuda:
+        B, nh, lora = q_lat.shape
+        if splits is None:
+            splits = _mla_splits(B, nh, ckv.shape[1])
+        out = torch.empty(B, nh, lora, dtype=q_lat.dtype, device=q_lat.device)
+        partials = None
+        if splits > 1:
+            partials = torch.empty(B * nh * splits * (lora + 2),
+                                   dtype=torch.float32, device=q_lat.device)
+        _native().mla_decode(q_lat.contiguous(), q_pe.contiguous(), ckv, kpe,
+                             lens, out, float(scale), partials, int(splits))
+        return out
+    return ref.mla_decode(q_lat, q_pe, ckv, kpe, lens, scale)
+
+
 _PREFILL_DIMS = {(128, 128), (64, 64), (192, 128), (96, 96)}
 
 

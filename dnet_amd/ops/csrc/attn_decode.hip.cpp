@@ -545,13 +545,18 @@ __global__ void attn_combine_kernel(const float* __restrict__ partials,
 void attn_combine(torch::Tensor partials, c10::optional<torch::Tensor> sinks,
                   torch::Tensor out, int64_t splits) {
   const int64_t B = out.size(0), Hq = out.size(1), DV = out.size(2);
-  DNET_CHECK(DV == 64 || DV == 128, "combine DV 64/128");
+  DNET_CHECK(DV == 64 || DV == 128 || DV == 512, "combine DV 64/128/512");
   DNET_CHECK(partials.is_contiguous() && out.is_contiguous(), "contig");
   DNET_CHECK(partials.numel() >= B * Hq * splits * (DV + 2), "partials size");
   auto stream = current_stream();
   const short* skp = sinks.has_value() ? (const short*)sinks->data_ptr()
                                        : nullptr;
-  if (DV == 128)
+  if (DV == 512)   // latent MLA (mla_decode.hip.cpp): 8 dims per lane
+    hipLaunchKernelGGL((attn_combine_kernel<512>), dim3((unsigned)(B * Hq)),
+                       dim3(kWave), 0, stream,
+                       (const float*)partials.data_ptr(), skp,
+                       (short*)out.data_ptr(), (int)Hq, (int)splits);
+  else if (DV == 128)
     hipLaunchKernelGGL((attn_combine_kernel<128>), dim3((unsigned)(B * Hq)),
                        dim3(kWave), 0, stream,
                        (const float*)partials.data_ptr(), skp,

@@ -25,6 +25,10 @@ void attn_prefill(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                   int64_t q_off, int64_t window, double scale);
 void attn_combine(torch::Tensor partials, c10::optional<torch::Tensor> sinks,
                   torch::Tensor out, int64_t splits);
+void mla_decode(torch::Tensor q_lat, torch::Tensor q_pe, torch::Tensor ckv,
+                torch::Tensor kpe, torch::Tensor lens, torch::Tensor out,
+                double scale, c10::optional<torch::Tensor> partials,
+                int64_t splits);
 void rope_append_f32(torch::Tensor src, c10::optional<torch::Tensor> bias,
                      torch::Tensor qout, int64_t Hkv, torch::Tensor kcache,
                      torch::Tensor vcache, torch::Tensor pos,
@@ -113,6 +117,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"));
   m.def("attn_combine", &dnet::attn_combine,
         "merge split/rank flash-decode partials");
+  m.def("mla_decode", &dnet::mla_decode,
+        "MFMA flash-decode over the latent (absorbed) MLA KV cache",
+        py::arg("q_lat"), py::arg("q_pe"), py::arg("ckv"), py::arg("kpe"),
+        py::arg("lens"), py::arg("out"), py::arg("scale"),
+        py::arg("partials"), py::arg("splits"));
   m.def("rope_append", &dnet::rope_append, "fused RoPE + KV append (decode)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kcache"),
         py::arg("vcache"), py::arg("pos"), py::arg("cos_table"),

@@ -240,6 +240,25 @@ def attn_decode(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
     return out
 
 
+def mla_decode(q_lat: torch.Tensor, q_pe: torch.Tensor, ckv: torch.Tensor,
+               kpe: torch.Tensor, lens: torch.Tensor,
+               scale: float) -> torch.Tensor:
+    """Absorbed-MLA decode attention in fp32: q_lat [B,nh,L], q_pe
+    [B,nh,R], ckv [B,S,L], kpe [B,S,R], lens [B] -> [B,nh,L]; row b attends
+    positions [0, len[b]) of the shared latent stream, whose first L
+    columns are also the value."""
+    out = torch.zeros_like(q_lat)
+    for b in range(q_lat.shape[0]):
+        ln = int(lens[b])
+        if ln == 0:
+            continue
+        c = ckv[b, :ln].float()
+        s = (q_lat[b].float() @ c.T
+             + q_pe[b].float() @ kpe[b, :ln].float().T) * scale
+        out[b] = (torch.softmax(s, dim=-1) @ c).to(q_lat.dtype)
+    return out
+
+
 def rope_tables(smax: int, d: int, theta: float,
                 device=None, scaling: dict | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Precompute [Smax, D/2] f32 cos/sin tables (neox convention).
