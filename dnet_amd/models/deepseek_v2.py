@@ -78,6 +78,9 @@ class MLAKVCache(KVCache):
 class DeepseekV2RingModel(RingModel):
     model_type = "deepseek_v2"
     model_types = ["deepseek_v2", "deepseek_v3"]
+    # rows from which the routed experts take the token-routed MFMA path
+    # (see MoERingModel.ROWS_MOE_MIN_T)
+    ROWS_MOE_MIN_T = int(os.environ.get("DNET_MOE_ROWS_T", "65"))
 
     def __init__(self, cfg: ModelConfig, layer_ids, device, is_first, is_last,
                  smax: int = 4096, tp_rank: int = 0, tp_size: int = 1,
@@ -480,7 +483,26 @@ class DeepseekV2RingModel(RingModel):
             if c.norm_topk_prob:
                 weights = weights / weights.sum(-1, keepdim=True)
         T = y.shape[0]
-        if T <= 64 and lw.experts_gateup[0].bits in (8, 16):
+        st = None
+        if (y.is_cuda and T >= self.ROWS_MOE_MIN_T and T > 64
+                and lw.experts_gateup[0].bits in (8, 16)):
+            # token-routed MFMA path (models/moe.py); same EP rule
+            from .moe import stack_experts, stack_route_weights, moe_rows
+            local = [e for e in range(c.num_experts)
+                     if self.tp_size <= 1 or e % self.tp_size == self.tp_rank]
+            st = stack_experts(lw, local)
+            if not ops.moe_rows_supported(st["gw"], y.shape[1],
+                                          st["gw"].shape[1] // 2,
+                                          st["dw"].shape[1], st["group"],
+                                          st["packed"]):
+                st = None
+        if st is not None:
+            we = torch.zeros(T, c.num_experts, dtype=torch.float32,
+                             device=y.device)
+            we.scatter_(1, idx, weights)
+            we = stack_route_weights(st, we, self.tp_size, self.tp_rank)
+            out = moe_rows(y, st, we, c.num_experts_per_tok)
+        elif T <= 64 and lw.experts_gateup[0].bits in (8, 16):
             # grouped-expert kernels (graph-safe; unrouted experts skipped
             # on device) — see models/moe.py. EP: e % tp == rank; partial
             # sums reduced by the caller.

@@ -86,6 +86,19 @@ def stack_route_weights(st: dict, we: torch.Tensor, tp_size: int,
     return we
 
 
+def moe_rows(y: torch.Tensor, st: dict, we: torch.Tensor, topk: int,
+             glu: int = 0, alpha: float = 1.702, limit: float = 7.0
+             ) -> torch.Tensor:
+    """Token-routed expert MLP over a stacked bank: y [T, K] bf16 and the
+    stack-aligned dense routing weights we [T, E] -> [T, H] f32. Device
+    only: no host sync, so prefill stays asynchronous."""
+    plan = ops.moe_route(we, topk)
+    act = ops.moe_gateup_rows(y.contiguous(), st["gw"], st["gs"], st["gb"], plan,
+                              st["group"], st["packed"], glu, alpha, limit)
+    return ops.moe_down_rows(act, st["dw"], st["ds"], st["db"], we, plan,
+                             st["group"], st["packed"])
+
+
 class MoERingModel(RingModel):
     model_type = "mixtral"
     model_types = ["mixtral", "qwen2_moe", "qwen3_moe"]
@@ -213,7 +226,11 @@ class MoERingModel(RingModel):
     # skipped per-block on device, so a single stream reads only the top-k
     # experts' weights)
     DENSE_MOE_MAX_T = int(os.environ.get("DNET_DENSE_MOE_T", "64"))
-    GLU = 0                  # 0 = SwiGLU, 1 = gpt-oss clamped GLU
+    # from this many rows (and above DENSE_MOE_MAX_T), banks that
+    # ops.moe_rows_supported accepts take the token-routed MFMA path
+    # instead of the per-expert loop
+    ROWS_MOE_MIN_T = int(os.environ.get("DNET_MOE_ROWS_T", "65"))
+    GLU = 0                 # 0 = SwiGLU, 1 = gpt-oss clamped GLU
     GLU_ALPHA = 1.702
     GLU_LIMIT = 7.0
 
@@ -268,6 +285,23 @@ class MoERingModel(RingModel):
             if getattr(lw, "shared_gateup", None) is not None:
                 out = out + self._shared_expert(y, lw)
             return out.to(y.dtype)
+        if (y.is_cuda and T >= self.ROWS_MOE_MIN_T
+                and T > self.DENSE_MOE_MAX_T
+                and (eg0.bits in (8, 16) or eg0.mxfp4)):
+            st = self._expert_stack(lw)
+            if ops.moe_rows_supported(st["gw"], y.shape[1],
+                                      st["gw"].shape[1] // 2,
+                                      st["dw"].shape[1], st["group"],
+                                      st["packed"]):
+                we = torch.zeros(T, c.num_experts, dtype=torch.float32,
+                                 device=y.device)
+                we.scatter_(1, idx, weights)
+                we = stack_route_weights(st, we, self.tp_size, self.tp_rank)
+                out = moe_rows(y, st, we, c.num_experts_per_tok, self.GLU,
+                               self.GLU_ALPHA, self.GLU_LIMIT)
+                if getattr(lw, "shared_gateup", None) is not None:
+                    out = out + self._shared_expert(y, lw)
+                return out.to(y.dtype)
         out = torch.zeros_like(y, dtype=torch.float32)
         for e in range(c.num_experts):
             if self.tp_size > 1 and e % self.tp_size != self.tp_rank:

@@ -528,6 +528,104 @@ def moe_down(act: torch.Tensor, w: torch.Tensor, scales, bias,
     return ref.moe_down(act, w, scales, bias, we, group, packed)
 
 
+def moe_rows_supported(w: torch.Tensor, K: int, I: int, H: int, group: int,
+                       packed: bool) -> bool:
+    """Should the models send a stacked expert bank ``w`` through the
+    token-routed MFMA path (moe_route / moe_gateup_rows / moe_down_rows)?
+    True for mxfp4 banks (uint8 nibble rows, e8m0 scales, block 32) with
+    every dim a multiple of 64.
+
+    The kernels also run bf16 banks and int8 banks in the pack_int8_mfma
+    layout (group % 64 == 0), and the ops accept them, but at 8192 rows
+    they measured 2-3x slower than the per-expert loop (docs/KERNELS.md,
+    "MoE rows"), so those formats stay on the loop, as do unpacked int8
+    and grouped int4 (also uint8, group 128), which the kernels do not
+    serve at all."""
+    if K % 64 or I % 64 or H % 64:
+        return False
+    return bool(w.dtype == torch.uint8 and group == 32 and not packed)
+
+
+def moe_route(we: torch.Tensor, topk: int) -> dict:
+    """Sort the routed (token, expert) pairs of dense routing weights
+    we [T, E] f32 by expert. (t, e) is routed iff we[t, e] != 0; ``topk``
+    (host int) bounds the non-zeros per row, rows may hold fewer or none.
+    Routed pairs get consecutive slots, experts ascending and tokens
+    ascending inside an expert. Returns a plan of int32 device tensors and
+    host-known capacities:
+
+    counts [E], offsets [E+1]   expert e owns slots offsets[e]:offsets[e+1]
+    slot_token [slots_cap]      slot -> token, -1 past the live slots
+    token_slots [T, topk]       token -> its slots, e ascending, then -1
+    tiles [tiles_cap, 3]        (expert, first slot, rows <= 64) per GEMM
+                                tile, live ones first; zeros after
+    ntiles [1]                  number of live tiles
+    T, E, topk, slots_cap, tiles_cap   host ints
+
+    Two launches, no host sync, no atomics; the plan is a function of
+    ``we != 0`` alone."""
+    if not we.is_cuda:
+        return ref.moe_route(we, int(topk))
+    T, E = we.shape
+    topk = int(topk)
+    slots_cap, tiles_cap = ref.moe_plan_caps(T, E, topk)
+    i32 = dict(dtype=torch.int32, device=we.device)
+    plan = {"counts": torch.empty(E, **i32),
+            "offsets": torch.empty(E + 1, **i32),
+            "slot_token": torch.empty(slots_cap, **i32),
+            "token_slots": torch.empty(T, topk, **i32),
+            "tiles": torch.empty(tiles_cap, 3, **i32),
+            "ntiles": torch.empty(1, **i32), "T": T, "E": E, "topk": topk,
+            "slots_cap": slots_cap, "tiles_cap": tiles_cap}
+    blockcnt = torch.empty(-(-T // 256) * E, **i32)
+    _native().moe_route(we.contiguous(), blockcnt, plan["counts"],
+                        plan["offsets"], plan["slot_token"],
+                        plan["token_slots"], plan["tiles"], plan["ntiles"],
+                        topk)
+    return plan
+
+
+def moe_gateup_rows(x: torch.Tensor, gw: torch.Tensor, gs, gb, plan: dict,
+                    group: int = 0, packed: bool = False, glu: int = 0,
+                    alpha: float = 1.702, limit: float = 7.0) -> torch.Tensor:
+    """Routed gate+up with fused GLU: x [T,K] bf16, stacked gw [E,2I,K]
+    -> act [slots_cap, I] bf16, compact in the plan's slot order:
+    act[slot] = glu(x[t] . Wg[e]^T + bg, x[t] . Wu[e]^T + bu). Rows past
+    the live slots are never written (nor read by moe_down_rows). A slot's
+    bits depend on its own token only."""
+    if x.is_cuda:
+        act = torch.empty(plan["slots_cap"], gw.shape[1] // 2,
+                          dtype=torch.bfloat16, device=x.device)
+        _native().moe_rows_gateup(x, gw, gs, gb, plan["slot_token"],
+                                  plan["tiles"], plan["ntiles"], act, group,
+                                  packed, glu, alpha, limit)
+        return act
+    return ref.moe_gateup_rows(x, gw, gs, gb, plan, group, packed, glu,
+                               alpha, limit)
+
+
+def moe_down_rows(act: torch.Tensor, dw: torch.Tensor, ds, db,
+                  we: torch.Tensor, plan: dict, group: int = 0,
+                  packed: bool = False) -> torch.Tensor:
+    """Routed down projection and combine: act [slots_cap, I], stacked dw
+    [E,H,I], we [T,E] (the weights the plan was made from) -> out [T,H]
+    f32, out[t] = sum_e we[t,e] * (act[slot(t,e)] . Wd[e]^T + bd[e]) over
+    the token's slots in ascending-e order; exact zeros for a token with
+    no routed expert. Fixed summation order, no atomics."""
+    if act.is_cuda:
+        H = dw.shape[1]
+        y = torch.empty(plan["slots_cap"], H, dtype=torch.float32,
+                        device=act.device)
+        out = torch.empty(plan["T"], H, dtype=torch.float32,
+                          device=act.device)
+        _native().moe_rows_down(act, dw, ds, db, we.contiguous(),
+                                plan["slot_token"], plan["token_slots"],
+                                plan["tiles"], plan["ntiles"], y, out, group,
+                                packed)
+        return out
+    return ref.moe_down_rows(act, dw, ds, db, we, plan, group, packed)
+
+
 quantize_int8 = ref.quantize_int8
 quantize_int4 = ref.quantize_int4
 pack_int8_mfma = ref.pack_int8_mfma

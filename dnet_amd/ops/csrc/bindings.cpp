@@ -79,6 +79,22 @@ void moe_down(torch::Tensor act, torch::Tensor w,
               c10::optional<torch::Tensor> scales,
               c10::optional<torch::Tensor> bias, torch::Tensor we,
               torch::Tensor out, int64_t group, bool packed);
+void moe_route(torch::Tensor we, torch::Tensor blockcnt, torch::Tensor counts,
+               torch::Tensor offsets, torch::Tensor slot_token,
+               torch::Tensor token_slots, torch::Tensor tiles,
+               torch::Tensor ntiles, int64_t topk);
+void moe_rows_gateup(torch::Tensor x, torch::Tensor w,
+                     c10::optional<torch::Tensor> scales,
+                     c10::optional<torch::Tensor> bias,
+                     torch::Tensor slot_token, torch::Tensor tiles,
+                     torch::Tensor ntiles, torch::Tensor act, int64_t group,
+                     bool packed, int64_t glu, double alpha, double limit);
+void moe_rows_down(torch::Tensor act, torch::Tensor w,
+                   c10::optional<torch::Tensor> scales,
+                   c10::optional<torch::Tensor> bias, torch::Tensor we,
+                   torch::Tensor slot_token, torch::Tensor token_slots,
+                   torch::Tensor tiles, torch::Tensor ntiles, torch::Tensor y,
+                   torch::Tensor out, int64_t group, bool packed);
 void col_norm2(torch::Tensor x, torch::Tensor norms);
 void gather_cols(torch::Tensor x, torch::Tensor idx, torch::Tensor out);
 void scatter_cols(torch::Tensor in, torch::Tensor idx, torch::Tensor out);
@@ -174,6 +190,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped MoE gate+up GEMV with fused GLU and expert skip");
   m.def("moe_down", &dnet::moe_down,
         "grouped MoE down GEMV with weighted f32 accumulation");
+  m.def("moe_route", &dnet::moe_route,
+        "sort routed (token, expert) pairs by expert: slots, maps, tiles");
+  m.def("moe_rows_gateup", &dnet::moe_rows_gateup,
+        "token-routed MFMA gate/up GEMM with fused GLU over the tile list");
+  m.def("moe_rows_down", &dnet::moe_rows_down,
+        "token-routed MFMA down GEMM + fixed-order per-token combine");
   m.def("col_norm2", &dnet::col_norm2, "per-column L2 norms");
   m.def("gather_cols", &dnet::gather_cols, "pack kept columns");
   m.def("scatter_cols", &dnet::scatter_cols, "zero + scatter kept columns");

@@ -45,6 +45,18 @@ __device__ __forceinline__ short f2bits(const float f) {
   return (short)((u + rounding) >> 16);
 }
 
+// MFMA fragment types (v_mfma_f32_16x16x32_bf16: 8 bf16 of A/B and 4 f32
+// of C per lane) and the int8 -> bf16(q*s) fragment dequant.
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+__device__ __forceinline__ bf16x8 deq8(const int8_t* q, const float s) {
+  bf16x8 b;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) b[j] = (__bf16)((float)q[j] * s);
+  return b;
+}
+
 // Wave-wide f32 sum reduction (64 lanes).
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

@@ -25,15 +25,7 @@
 
 namespace dnet {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ bf16x8 deq8(const int8_t* q, const float s) {
-  bf16x8 b;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) b[j] = (__bf16)((float)q[j] * s);
-  return b;
-}
+// bf16x8, f32x4 and deq8 live in common.h (shared with moe_rows.hip.cpp).
 
 // 4 packed nibble-bytes (offset-8) -> 8 bf16 values * scale
 __device__ __forceinline__ bf16x8 deq4(const uint8_t* qb, const float s) {

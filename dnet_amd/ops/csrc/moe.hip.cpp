@@ -20,7 +20,7 @@
 // tile — data-dependent work without host syncs, so the pair stays
 // hipGraph-capturable (reference counterpart: the MLX MoE gather path in
 // src/dnet/core/models/gpt_oss.py).
-#include "common.h"
+#include "moe_common.h"
 
 namespace dnet {
 
@@ -51,17 +51,7 @@ __device__ __forceinline__ float mxfp4_val(const int nib, const int ebits) {
   return bits2f((short)bits);
 }
 
-// GLU = 0: silu(g) * u   GLU = 1: gpt-oss clamped (u+1) * g * sigmoid(g*a)
-template <int GLU>
-__device__ __forceinline__ float apply_glu(float g, float u, const float alpha,
-                                           const float limit) {
-  if (GLU == 1) {
-    g = fminf(g, limit);
-    u = fminf(fmaxf(u, -limit), limit);
-    return (u + 1.f) * g / (1.f + __expf(-g * alpha));
-  }
-  return g / (1.f + __expf(-g)) * u;
-}
+// apply_glu lives in moe_common.h (shared with moe_rows.hip.cpp).
 
 // QMODE: 0 = bf16, 1 = grouped int8, 2 = mxfp4 (nibble rows + e8m0)
 // launch bounds: M<=8 keeps the tight 128-VGPR budget (measured faster

@@ -477,6 +477,102 @@ def moe_down(act: torch.Tensor, w: torch.Tensor, scales, bias,
     return (we.t().unsqueeze(-1) * d).sum(dim=0)
 
 
+MOE_TILE_ROWS = 64
+
+
+def moe_plan_caps(T: int, E: int, topk: int) -> tuple[int, int]:
+    """(slots_cap, tiles_cap) of a routing plan, from host-known sizes:
+    at most min(topk, E) slots per token; sum_e ceil(c_e / 64) is at most
+    slots / 64 + E, and an expert holds a token at most once."""
+    slots_cap = T * min(topk, E)
+    tiles_cap = min(slots_cap // MOE_TILE_ROWS + E, E * -(-T // MOE_TILE_ROWS))
+    return slots_cap, tiles_cap
+
+
+def moe_route(we: torch.Tensor, topk: int) -> dict:
+    """Routing plan of dense weights we [T, E] ((t, e) routed iff
+    we[t, e] != 0, at most topk per row); layout in ops.moe_route."""
+    T, E = we.shape
+    slots_cap, tiles_cap = moe_plan_caps(T, E, topk)
+    i32 = dict(dtype=torch.int32, device=we.device)
+    nz = we != 0
+    counts = nz.sum(0)
+    offsets = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+    e_idx, t_idx = nz.t().nonzero(as_tuple=True)   # e ascending, then t
+    slot_token = torch.full((slots_cap,), -1, **i32)
+    slot_token[:t_idx.numel()] = t_idx.to(torch.int32)
+    token_slots = torch.full((T, topk), -1, **i32)
+    rank = nz.cumsum(1)[t_idx, e_idx] - 1           # position in the row
+    token_slots[t_idx, rank] = torch.arange(t_idx.numel(), **i32)
+    tiles = torch.zeros(tiles_cap, 3, **i32)
+    n = 0
+    for e in range(E):
+        for s in range(0, int(counts[e]), MOE_TILE_ROWS):
+            tiles[n] = torch.tensor(
+                [e, int(offsets[e]) + s,
+                 min(MOE_TILE_ROWS, int(counts[e]) - s)], **i32)
+            n += 1
+    return {"counts": counts.to(torch.int32),
+            "offsets": offsets.to(torch.int32), "slot_token": slot_token,
+            "token_slots": token_slots, "tiles": tiles,
+            "ntiles": torch.tensor([n], **i32), "T": T, "E": E,
+            "topk": topk, "slots_cap": slots_cap, "tiles_cap": tiles_cap}
+
+
+def moe_gateup_rows(x: torch.Tensor, w: torch.Tensor, scales, bias,
+                    plan: dict, group: int = 0, packed: bool = False,
+                    glu: int = 0, alpha: float = 1.702, limit: float = 7.0
+                    ) -> torch.Tensor:
+    """x [T,K], w [E,2I,K] -> act [slots_cap, I] bf16 in slot order (rows
+    past the live slots are zero here, undefined on the GPU)."""
+    wf = _moe_dense_w(w, scales, group, packed)
+    i = wf.shape[1] // 2
+    act = torch.zeros(plan["slots_cap"], i, dtype=torch.bfloat16,
+                      device=x.device)
+    off = plan["offsets"].tolist()
+    for e in range(plan["E"]):
+        s0, s1 = off[e], off[e + 1]
+        if s0 == s1:
+            continue
+        gu = x[plan["slot_token"][s0:s1].long()].float() @ wf[e].t()
+        if bias is not None:
+            gu = gu + bias[e].float()
+        g, u = gu[:, :i], gu[:, i:]
+        if glu == 1:
+            g = g.clamp(max=limit)
+            u = u.clamp(min=-limit, max=limit)
+            a = (u + 1.0) * g * torch.sigmoid(g * alpha)
+        else:
+            a = torch.nn.functional.silu(g) * u
+        act[s0:s1] = a.to(torch.bfloat16)
+    return act
+
+
+def moe_down_rows(act: torch.Tensor, w: torch.Tensor, scales, bias,
+                  we: torch.Tensor, plan: dict, group: int = 0,
+                  packed: bool = False) -> torch.Tensor:
+    """act [slots_cap, I], w [E,H,I], we [T,E] -> out [T,H] f32: each
+    token's expert outputs summed over its slots in ascending-e order."""
+    wf = _moe_dense_w(w, scales, group, packed)
+    y = torch.zeros(plan["slots_cap"], wf.shape[1], dtype=torch.float32,
+                    device=act.device)
+    off = plan["offsets"].tolist()
+    for e in range(plan["E"]):
+        s0, s1 = off[e], off[e + 1]
+        if s0 == s1:
+            continue
+        d = act[s0:s1].float() @ wf[e].t()
+        if bias is not None:
+            d = d + bias[e].float()
+        y[s0:s1] = we[plan["slot_token"][s0:s1].long(), e].unsqueeze(1) * d
+    out = torch.zeros(plan["T"], wf.shape[1], dtype=torch.float32,
+                      device=act.device)
+    ts = plan["token_slots"].long()
+    for j in range(plan["topk"]):
+        out += torch.where(ts[:, j:j + 1] >= 0, y[ts[:, j].clamp(min=0)], 0.0)
+    return out
+
+
 _MXFP4_LUT = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0,
               -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0]
 
