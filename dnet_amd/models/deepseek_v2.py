@@ -5,8 +5,9 @@ qk_nope + qk_rope split head dims). The MLA projections (q, kv_a with
 shared rope key, kv_a layernorm, kv_b) run through the fused GEMV/GEMM
 linears; decode attention runs on the native flash-decode kernel with the
 MLA head-dim pair (qk 192 / v 128) over the per-head cache, or on the
-latent flash-decode kernel (ops.mla_decode) over the compressed cache.
-MoE layers use
+latent flash-decode kernel (ops.mla_decode) over the compressed cache;
+a continuation prefill chunk attends that cache in place too
+(ops.mla_prefill). MoE layers use
 routed top-k (softmax scoring, greedy) * routed_scaling_factor + shared
 experts; the first ``first_k_dense_replace`` layers are dense.
 """
@@ -81,6 +82,11 @@ class DeepseekV2RingModel(RingModel):
     # rows from which the routed experts take the token-routed MFMA path
     # (see MoERingModel.ROWS_MOE_MIN_T)
     ROWS_MOE_MIN_T = int(os.environ.get("DNET_MOE_ROWS_T", "65"))
+    # continuation-prefill chunks (p0 > 0) of at most this many tokens
+    # attend the latent cache in place (ops.mla_prefill); longer ones
+    # expand it through kv_b. 512 is the largest T measured, and the kernel
+    # path was ahead there (profiles/r09_mla_prefill.md)
+    MLA_PREFILL_MAX_T = int(os.environ.get("DNET_MLA_PREFILL_T", "512"))
 
     def __init__(self, cfg: ModelConfig, layer_ids, device, is_first, is_last,
                  smax: int = 4096, tp_rank: int = 0, tp_size: int = 1,
@@ -299,12 +305,16 @@ class DeepseekV2RingModel(RingModel):
     def _mla_qkv(self, y: torch.Tensor, lw, positions):
         """y [T, H] -> q [T, Hq, kd], k [T, Hq, kd], v [T, Hq, vd] (roped),
         plus the latent pieces (c_kv normed, k_pe roped)."""
-        c = self.cfg
-        T = y.shape[0]
-        nope, rope, vd = c.qk_nope_head_dim, c.qk_rope_head_dim, c.v_head_dim
-        nh = self.nh
         q_nope, q_pe = self._mla_q(y, lw, positions)
         c_kv, k_pe = self._mla_latent(y, lw, positions)
+        return self._mla_expand(q_nope, q_pe, c_kv, k_pe, lw)
+
+    def _mla_expand(self, q_nope, q_pe, c_kv, k_pe, lw):
+        """The per-head half of _mla_qkv: kv_b over the fresh latents."""
+        c = self.cfg
+        T = c_kv.shape[0]
+        nope, rope, vd = c.qk_nope_head_dim, c.qk_rope_head_dim, c.v_head_dim
+        nh = self.nh
         kv = lw.kv_b(c_kv).view(T, nh, nope + vd)
         k_nope, v = kv[..., :nope], kv[..., nope:]
         q = torch.cat([q_nope, q_pe], dim=-1)
@@ -378,6 +388,22 @@ class DeepseekV2RingModel(RingModel):
         olat = torch.einsum("bhs,bsl->bhl", p, ckv)
         return torch.einsum("bhl,hvl->bhv", olat, wv)
 
+    def _latent_prefill(self, y, lw, kv, li, positions, B, T, p0):
+        """One layer's continuation-prefill attention in absorbed form:
+        y [B*T, H] -> [B*T, nh*vd]. The chunk's latents are appended, then
+        ops.mla_prefill reads the cache in place; neither kv_b nor a
+        per-head K/V is computed."""
+        q_nope, q_pe = self._mla_q(y, lw, positions)
+        c_kv, k_pe = self._mla_latent(y, lw, positions)
+        kv.ckv[li][:, p0:p0 + T] = c_kv.view(B, T, -1)
+        kv.kpe[li][:, p0:p0 + T] = k_pe.view(B, T, -1)
+        wk, wv = self._absorbed(lw)
+        q_eff = torch.einsum("bthn,hnl->bthl",
+                             q_nope.view(B, T, self.nh, -1), wk)
+        olat = ops.mla_prefill(q_eff, q_pe.view(B, T, self.nh, -1),
+                               kv.ckv[li], kv.kpe[li], p0, self.scale)
+        return torch.einsum("bthl,hvl->bthv", olat, wv).reshape(B * T, -1)
+
     def decode_window(self, h, layer_ids, kv):
         c = self.cfg
         B = h.shape[0]
@@ -415,39 +441,52 @@ class DeepseekV2RingModel(RingModel):
         h.add_(delta)
         return h
 
+    def _expanded_prefill(self, y, lw, kv, li, positions, B, T, p0):
+        """One layer's prefill attention over per-head k/v: y [B*T, H] ->
+        [B*T, nh*vd]. Appends the chunk to the cache (either layout)."""
+        q, k, v, c_kv, k_pe = self._mla_qkv(y, lw, positions)
+        kd, vd = k.shape[-1], v.shape[-1]
+        q = q.view(B, T, self.nh, kd).transpose(1, 2)
+        if kv.latent:
+            kv.ckv[li][:, p0:p0 + T] = c_kv.view(B, T, -1)
+            kv.kpe[li][:, p0:p0 + T] = k_pe.view(B, T, -1)
+            # continuation prefill: expand past+current k/v from the
+            # latent stream transiently (steady-state memory stays 576
+            # wide); the fresh window's k/v were just computed
+            if p0 > 0:
+                kf, vf = self._expand_kv(kv, li, lw, p0 + T)
+            else:
+                kf = k.view(B, T, self.nh, kd).transpose(1, 2)
+                vf = v.view(B, T, self.nh, vd).transpose(1, 2)
+        else:
+            k = k.view(B, T, self.nh, kd).transpose(1, 2)
+            v = v.view(B, T, self.nh, vd).transpose(1, 2)
+            kv.k[li][:, :, p0:p0 + T] = k
+            kv.v[li][:, :, p0:p0 + T] = v
+            kf = kv.k[li][:, :, :p0 + T]
+            vf = kv.v[li][:, :, :p0 + T]
+        attn = _chunked_causal_attention(q, kf, vf, self.scale, p0)
+        return attn.transpose(1, 2).reshape(B * T, -1).contiguous()
+
     def prefill_window(self, h, layer_ids, kv, p0: int):
         c = self.cfg
         B, T, H = h.shape
         positions = torch.arange(p0, p0 + T, device=h.device)
+        # a short continuation chunk attends the latent cache in place
+        absorbed = (kv.latent and p0 > 0 and h.is_cuda
+                    and ops.mla_prefill_supported(c.kv_lora_rank,
+                                                  c.qk_rope_head_dim)
+                    and os.environ.get("DNET_MLA_PREFILL") != "0"
+                    and T <= self.MLA_PREFILL_MAX_T)
         for lid in layer_ids:
             lw = self._layer(lid)
             flat = h.view(B * T, H)
             y = ops.rmsnorm(flat, None, lw.attn_norm, c.rms_eps)
-            q, k, v, c_kv, k_pe = self._mla_qkv(y, lw, positions.repeat(B))
-            kd, vd = k.shape[-1], v.shape[-1]
-            q = q.view(B, T, self.nh, kd).transpose(1, 2)
-            li = kv.local[lid]
-            if kv.latent:
-                kv.ckv[li][:, p0:p0 + T] = c_kv.view(B, T, -1)
-                kv.kpe[li][:, p0:p0 + T] = k_pe.view(B, T, -1)
-                # continuation prefill: expand past+current k/v from the
-                # latent stream transiently (steady-state memory stays 576
-                # wide); the fresh window's k/v were just computed
-                if p0 > 0:
-                    kf, vf = self._expand_kv(kv, li, lw, p0 + T)
-                else:
-                    kf = k.view(B, T, self.nh, kd).transpose(1, 2)
-                    vf = v.view(B, T, self.nh, vd).transpose(1, 2)
-            else:
-                k = k.view(B, T, self.nh, kd).transpose(1, 2)
-                v = v.view(B, T, self.nh, vd).transpose(1, 2)
-                kv.k[li][:, :, p0:p0 + T] = k
-                kv.v[li][:, :, p0:p0 + T] = v
-                kf = kv.k[li][:, :, :p0 + T]
-                vf = kv.v[li][:, :, :p0 + T]
-            attn = _chunked_causal_attention(q, kf, vf, self.scale, p0)
-            o = self._tp_reduce(
-                lw.o(attn.transpose(1, 2).reshape(B * T, -1).contiguous()))
+            attend = (self._latent_prefill if absorbed
+                      else self._expanded_prefill)
+            attn = attend(y, lw, kv, kv.local[lid], positions.repeat(B), B, T,
+                          p0)
+            o = self._tp_reduce(lw.o(attn))
             y2 = ops.rmsnorm(o, flat, lw.mlp_norm, c.rms_eps)
             flat.add_(self._tp_reduce(self._mlp_for(lid, y2, lw)))
         return h

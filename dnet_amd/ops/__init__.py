@@ -256,6 +256,55 @@ def mla_decode(q_lat: torch.Tensor, q_pe: torch.Tensor, ckv: torch.Tensor,
     return ref.mla_decode(q_lat, q_pe, ckv, kpe, lens, scale)
 
 
+def mla_prefill_supported(lora: int, rope: int) -> bool:
+    """Latent dims the HIP mla_prefill kernel serves (those of
+    mla_decode)."""
+    return (lora, rope) == (512, 64)
+
+
+def _mla_prefill_splits(b: int, t: int, nh: int, n: int) -> int:
+    # a block holds 4 (token, 16-head tile) items and 73 KB of LDS: split
+    # until ~512 blocks (2 per CU, as _mla_splits) while a split still owns
+    # two 64-position chunks of the n = q_off + T attended rows
+    groups = -(-(t * -(-nh // 16)) // 4)
+    chunks = -(-n // 64)
+    splits = 1
+    while b * groups * splits * 2 <= 512 and splits * 2 <= chunks // 2:
+        splits *= 2
+    return splits
+
+
+def mla_prefill(q_lat: torch.Tensor, q_pe: torch.Tensor, ckv: torch.Tensor,
+                kpe: torch.Tensor, q_off: int, scale: float,
+                splits: int | None = None) -> torch.Tensor:
+    """Absorbed-MLA continuation-prefill attention over the latent cache,
+    read in place.
+
+    q_lat [B,T,nh,512] (queries folded through W_k), q_pe [B,T,nh,64]
+    (roped), ckv [B,S,512], kpe [B,S,64] bf16 (rows contiguous, any
+    16-byte-aligned batch stride: ``MLAKVCache`` planes and their
+    ``slot()`` views) -> o_lat [B,T,nh,512]; token t sits at position
+    q_off + t and attends rows [0, q_off + t + 1), which must already hold
+    the chunk's own latents. Rows >= q_off + T are never read. ``splits``
+    (split-S factor) defaults to a heuristic over (B, T, nh, q_off + T).
+    Eager only (q_off is a host int)."""
+    if q_lat.is_cuda:
+        B, T, nh, lora = q_lat.shape
+        if splits is None:
+            splits = _mla_prefill_splits(B, T, nh, int(q_off) + T)
+        out = torch.empty(B, T, nh, lora, dtype=q_lat.dtype,
+                          device=q_lat.device)
+        partials = None
+        if splits > 1:
+            partials = torch.empty(B * T * nh * splits * (lora + 2),
+                                   dtype=torch.float32, device=q_lat.device)
+        _native().mla_prefill(q_lat.contiguous(), q_pe.contiguous(), ckv, kpe,
+                              out, int(q_off), float(scale), partials,
+                              int(splits))
+        return out
+    return ref.mla_prefill(q_lat, q_pe, ckv, kpe, int(q_off), scale)
+
+
 _PREFILL_DIMS = {(128, 128), (64, 64), (192, 128), (96, 96)}
 
 

@@ -29,6 +29,10 @@ void mla_decode(torch::Tensor q_lat, torch::Tensor q_pe, torch::Tensor ckv,
                 torch::Tensor kpe, torch::Tensor lens, torch::Tensor out,
                 double scale, c10::optional<torch::Tensor> partials,
                 int64_t splits);
+void mla_prefill(torch::Tensor q_lat, torch::Tensor q_pe, torch::Tensor ckv,
+                 torch::Tensor kpe, torch::Tensor out, int64_t q_off,
+                 double scale, c10::optional<torch::Tensor> partials,
+                 int64_t splits);
 void rope_append_f32(torch::Tensor src, c10::optional<torch::Tensor> bias,
                      torch::Tensor qout, int64_t Hkv, torch::Tensor kcache,
                      torch::Tensor vcache, torch::Tensor pos,
@@ -137,6 +141,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MFMA flash-decode over the latent (absorbed) MLA KV cache",
         py::arg("q_lat"), py::arg("q_pe"), py::arg("ckv"), py::arg("kpe"),
         py::arg("lens"), py::arg("out"), py::arg("scale"),
+        py::arg("partials"), py::arg("splits"));
+  m.def("mla_prefill", &dnet::mla_prefill,
+        "MFMA flash-prefill (causal continuation) over the latent MLA KV "
+        "cache",
+        py::arg("q_lat"), py::arg("q_pe"), py::arg("ckv"), py::arg("kpe"),
+        py::arg("out"), py::arg("q_off"), py::arg("scale"),
         py::arg("partials"), py::arg("splits"));
   m.def("rope_append", &dnet::rope_append, "fused RoPE + KV append (decode)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kcache"),

@@ -259,6 +259,19 @@ def mla_decode(q_lat: torch.Tensor, q_pe: torch.Tensor, ckv: torch.Tensor,
     return out
 
 
+def mla_prefill(q_lat: torch.Tensor, q_pe: torch.Tensor, ckv: torch.Tensor,
+                kpe: torch.Tensor, q_off: int, scale: float) -> torch.Tensor:
+    """Absorbed-MLA continuation prefill in fp32: q_lat [B,T,nh,L], q_pe
+    [B,T,nh,R] -> [B,T,nh,L]; token t is mla_decode at length
+    q_off + t + 1."""
+    B, T = q_lat.shape[:2]
+    out = torch.empty_like(q_lat)
+    for t in range(T):
+        lens = torch.full((B,), q_off + t + 1, dtype=torch.int32)
+        out[:, t] = mla_decode(q_lat[:, t], q_pe[:, t], ckv, kpe, lens, scale)
+    return out
+
+
 def rope_tables(smax: int, d: int, theta: float,
                 device=None, scaling: dict | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Precompute [Smax, D/2] f32 cos/sin tables (neox convention).
