@@ -491,6 +491,11 @@ class DeepseekV2RingModel(RingModel):
             flat.add_(self._tp_reduce(self._mlp_for(lid, y2, lw)))
         return h
 
+    @staticmethod
+    def _int4_grouped(y: torch.Tensor, lw) -> bool:
+        from .moe import int4_grouped
+        return int4_grouped(y, lw)
+
     def _mlp_for(self, lid: int, y: torch.Tensor, lw) -> torch.Tensor:
         c = self.cfg
         if lw.gateup is not None:
@@ -541,7 +546,8 @@ class DeepseekV2RingModel(RingModel):
             we.scatter_(1, idx, weights)
             we = stack_route_weights(st, we, self.tp_size, self.tp_rank)
             out = moe_rows(y, st, we, c.num_experts_per_tok)
-        elif T <= 64 and lw.experts_gateup[0].bits in (8, 16):
+        elif T <= 64 and (lw.experts_gateup[0].bits in (8, 16)
+                          or self._int4_grouped(y, lw)):
             # grouped-expert kernels (graph-safe; unrouted experts skipped
             # on device) — see models/moe.py. EP: e % tp == rank; partial
             # sums reduced by the caller.

@@ -99,6 +99,24 @@ def moe_rows(y: torch.Tensor, st: dict, we: torch.Tensor, topk: int,
                              st["group"], st["packed"])
 
 
+def int4_grouped(y: torch.Tensor, lw: LayerWeights) -> bool:
+    """Do y's rows take the grouped MFMA pair for int4 banks (ops.moe_gateup
+    / moe_down)? GPU only, T <= 64, both projections int4 (a projection
+    that Linear.make stored as int8 keeps the whole bank on the loop) and
+    dims ops.moe_int4_supported accepts. DNET_MOE_INT4=0 keeps the loop."""
+    g0, d0 = lw.experts_gateup[0], lw.experts_down[0]
+    if not y.is_cuda or y.shape[0] > 64:
+        return False
+    if os.environ.get("DNET_MOE_INT4", "1") == "0":
+        return False
+    for lin in (g0, d0):
+        if lin.bits != 4 or lin.mxfp4 or lin.group != g0.group:
+            return False
+    return ops.moe_int4_supported(y.shape[1], g0.w.shape[0] // 2,
+                                  d0.w.shape[0], g0.group,
+                                  g0.packed and d0.packed)
+
+
 class MoERingModel(RingModel):
     model_type = "mixtral"
     model_types = ["mixtral", "qwen2_moe", "qwen3_moe"]
@@ -271,7 +289,8 @@ class MoERingModel(RingModel):
         weights, idx = self._route(logits)
         eg0 = lw.experts_gateup[0]
         if (T <= self.DENSE_MOE_MAX_T
-                and (eg0.bits in (8, 16) or eg0.mxfp4)):
+                and (eg0.bits in (8, 16) or eg0.mxfp4
+                     or int4_grouped(y, lw))):
             st = self._expert_stack(lw)
             we = torch.zeros(T, c.num_experts, dtype=torch.float32,
                              device=y.device)

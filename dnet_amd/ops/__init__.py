@@ -550,9 +550,12 @@ def moe_gateup(x: torch.Tensor, w: torch.Tensor, scales, bias,
                glu: int = 0, alpha: float = 1.702,
                limit: float = 7.0) -> torch.Tensor:
     """Grouped expert gate+up with fused GLU: x [M,K], stacked w [E,2I,K]
-    (bf16 or grouped-int8), we [M,E] f32 routing weights -> act [E,M,I].
-    Experts with all-zero we are skipped on GPU (their act rows hold
-    garbage; moe_down never reads them)."""
+    (bf16 or grouped-int8; uint8 nibbles [E,2I,K/2] with e8m0 uint8 scales
+    = mxfp4, with bf16 group scales = int4, which on the GPU takes the
+    MFMA kernels of moe_int4.hip.cpp and needs ``packed``, the
+    pack_int4_mfma layout, and M <= 64), we [M,E] f32 routing weights ->
+    act [E,M,I]. Experts with all-zero we are skipped on GPU (their act
+    rows hold garbage; moe_down never reads them)."""
     if x.is_cuda:
         e, i2, _ = w.shape
         act = torch.empty(e, x.shape[0], i2 // 2, dtype=torch.bfloat16,
@@ -570,11 +573,31 @@ def moe_down(act: torch.Tensor, w: torch.Tensor, scales, bias,
     """Grouped expert down projection, weighted f32 accumulation:
     act [E,M,I], stacked w [E,H,I], we [M,E] -> out [M,H] f32."""
     if act.is_cuda:
-        out = torch.zeros(act.shape[1], w.shape[1], dtype=torch.float32,
-                          device=act.device)
+        # the int4 kernels store every element; the others accumulate
+        int4 = w.dtype == torch.uint8 and scales.dtype == torch.bfloat16
+        out = (torch.empty if int4 else torch.zeros)(
+            act.shape[1], w.shape[1], dtype=torch.float32, device=act.device)
         _native().moe_down(act, w, scales, bias, we, out, group, packed)
         return out
     return ref.moe_down(act, w, scales, bias, we, group, packed)
+
+
+def moe_int4_supported(K: int, I: int, H: int, group: int,
+                       packed: bool) -> bool:
+    """Should the models send an int4 expert bank (gate/up [E,2I,K/2],
+    down [E,H,I/2], bf16 scales) with T <= 64 rows through moe_gateup /
+    moe_down on the GPU? The MFMA kernels take the pack_int4_mfma layout
+    with K, I and the group multiples of 128 and H a multiple of 16."""
+    if not packed or group <= 0 or group % 128:
+        return False
+    return not (K % 128 or I % 128 or K % group or I % group or H % 16)
+
+
+def moe_int4_force_ks(ks: int) -> None:
+    """Waves per column strip in the int4 MoE kernels: 0 picks by shape,
+    1 or 4 forces it (M > 32 always runs 1). Process-wide; for benchmarks
+    and tests."""
+    _native().moe_int4_force_ks(ks)
 
 
 def moe_rows_supported(w: torch.Tensor, K: int, I: int, H: int, group: int,

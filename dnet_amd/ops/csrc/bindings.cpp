@@ -83,6 +83,7 @@ void moe_down(torch::Tensor act, torch::Tensor w,
               c10::optional<torch::Tensor> scales,
               c10::optional<torch::Tensor> bias, torch::Tensor we,
               torch::Tensor out, int64_t group, bool packed);
+void moe_int4_force_ks(int64_t ks);
 void moe_route(torch::Tensor we, torch::Tensor blockcnt, torch::Tensor counts,
                torch::Tensor offsets, torch::Tensor slot_token,
                torch::Tensor token_slots, torch::Tensor tiles,
@@ -200,6 +201,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped MoE gate+up GEMV with fused GLU and expert skip");
   m.def("moe_down", &dnet::moe_down,
         "grouped MoE down GEMV with weighted f32 accumulation");
+  m.def("moe_int4_force_ks", &dnet::moe_int4_force_ks,
+        "int4 MoE kernels: waves per column strip, 0 = by shape, 1 or 4");
   m.def("moe_route", &dnet::moe_route,
         "sort routed (token, expert) pairs by expert: slots, maps, tiles");
   m.def("moe_rows_gateup", &dnet::moe_rows_gateup,

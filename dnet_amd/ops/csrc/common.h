@@ -46,7 +46,7 @@ __device__ __forceinline__ short f2bits(const float f) {
 }
 
 // MFMA fragment types (v_mfma_f32_16x16x32_bf16: 8 bf16 of A/B and 4 f32
-// of C per lane) and the int8 -> bf16(q*s) fragment dequant.
+// of C per lane) and the int8 / int4 -> bf16(q*s) fragment dequants.
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -54,6 +54,18 @@ __device__ __forceinline__ bf16x8 deq8(const int8_t* q, const float s) {
   bf16x8 b;
 #pragma unroll
   for (int j = 0; j < 8; ++j) b[j] = (__bf16)((float)q[j] * s);
+  return b;
+}
+
+// 4 packed nibble-bytes (offset-8) -> 8 bf16 values * scale
+__device__ __forceinline__ bf16x8 deq4(const uint8_t* qb, const float s) {
+  bf16x8 b;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int byte = qb[j];
+    b[2 * j] = (__bf16)((float)((byte & 0xF) - 8) * s);
+    b[2 * j + 1] = (__bf16)((float)((byte >> 4) - 8) * s);
+  }
   return b;
 }
 

@@ -25,19 +25,8 @@
 
 namespace dnet {
 
-// bf16x8, f32x4 and deq8 live in common.h (shared with moe_rows.hip.cpp).
-
-// 4 packed nibble-bytes (offset-8) -> 8 bf16 values * scale
-__device__ __forceinline__ bf16x8 deq4(const uint8_t* qb, const float s) {
-  bf16x8 b;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int byte = qb[j];
-    b[2 * j] = (__bf16)((float)((byte & 0xF) - 8) * s);
-    b[2 * j + 1] = (__bf16)((float)((byte >> 4) - 8) * s);
-  }
-  return b;
-}
+// bf16x8, f32x4, deq8 and deq4 live in common.h (shared with
+// moe_rows.hip.cpp and moe_int4.hip.cpp).
 
 // Opt-in reproducible split-k (set_splitk_exact, OFF by default; the
 // default path stores the raw f32 partials). When on, every partial is

@@ -339,6 +339,11 @@ void moe_gateup(torch::Tensor x, torch::Tensor w,
                 c10::optional<torch::Tensor> bias, torch::Tensor we,
                 torch::Tensor act, int64_t group, bool packed, int64_t glu,
                 double alpha, double limit) {
+  if (moe_bank_is_int4(w, scales)) {
+    DNET_CHECK(packed, "moe int4: the bank must be in pack_int4_mfma order");
+    return moe_int4_gateup(x, w, scales, bias, we, act, group, glu, alpha,
+                           limit);
+  }
   const int64_t M = x.size(0), K = x.size(1);
   const int64_t E = w.size(0), I2 = w.size(1), I = I2 / 2;
   // weight dtype selects the mode: bf16, int8 (kChar), mxfp4 nibble rows
@@ -410,6 +415,10 @@ void moe_down(torch::Tensor act, torch::Tensor w,
               c10::optional<torch::Tensor> scales,
               c10::optional<torch::Tensor> bias, torch::Tensor we,
               torch::Tensor out, int64_t group, bool packed) {
+  if (moe_bank_is_int4(w, scales)) {
+    DNET_CHECK(packed, "moe int4: the bank must be in pack_int4_mfma order");
+    return moe_int4_down(act, w, scales, bias, we, out, group);
+  }
   const int64_t E = w.size(0), H = w.size(1);
   const int64_t M = act.size(1), I = act.size(2);
   const bool mx4 = w.scalar_type() == torch::kByte;

@@ -205,6 +205,16 @@ def pack_int4_mfma(q4: torch.Tensor) -> torch.Tensor:
     return packed.contiguous()
 
 
+def unpack_int4_mfma(qp: torch.Tensor) -> torch.Tensor:
+    """Inverse of pack_int4_mfma: chunk-quad order -> row-major nibbles."""
+    n, kb = qp.shape
+    k = kb * 2
+    assert k % 128 == 0
+    vals = unpack_int4(qp) + 8               # [N, quad, slice, chunk, j]
+    v = vals.view(n, k // 128, 4, 4, 8).permute(0, 1, 3, 2, 4).reshape(n, k)
+    return (v[:, 0::2] | (v[:, 1::2] << 4)).to(torch.uint8).contiguous()
+
+
 def attn_decode(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                 pos: torch.Tensor, scale: float, window: int = 0,
                 sinks: torch.Tensor | None = None,
@@ -439,8 +449,16 @@ def swiglu(gu: torch.Tensor) -> torch.Tensor:
 
 def _moe_dense_w(w: torch.Tensor, scales, group: int, packed: bool
                  ) -> torch.Tensor:
-    """Stacked expert weights [E, N, K(/2)] (bf16, grouped-int8, or
-    mxfp4 nibble rows) -> f32."""
+    """Stacked expert weights [E, N, K(/2)] (bf16, grouped-int8, grouped
+    int4 or mxfp4 nibble rows) -> f32. The two uint8 formats are told
+    apart by their scales: bf16 = int4, e8m0 uint8 = mxfp4."""
+    if w.dtype == torch.uint8 and scales.dtype == torch.bfloat16:
+        e, n, kb = w.shape         # int4: [E, N, K/2] + bf16 [E, N, K/G]
+        q = w.reshape(e * n, kb)
+        if packed:
+            q = unpack_int4_mfma(q)
+        return dequant_int4(q, scales.reshape(e * n, -1), group).float().view(
+            e, n, kb * 2)
     if w.dtype == torch.uint8:     # mxfp4: [E, N, K/2] + e8m0 [E, N, K/32]
         e, n, kb = w.shape
         return dequant_mxfp4(w.reshape(e * n, kb),
