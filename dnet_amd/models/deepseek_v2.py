@@ -528,17 +528,18 @@ class DeepseekV2RingModel(RingModel):
                 weights = weights / weights.sum(-1, keepdim=True)
         T = y.shape[0]
         st = None
-        if (y.is_cuda and T >= self.ROWS_MOE_MIN_T and T > 64
-                and lw.experts_gateup[0].bits in (8, 16)):
+        from .moe import int4_rows
+        rows4 = int4_rows(y, lw, self.ROWS_MOE_MIN_T)
+        if rows4 or (y.is_cuda and T >= self.ROWS_MOE_MIN_T and T > 64
+                     and lw.experts_gateup[0].bits in (8, 16)):
             # token-routed MFMA path (models/moe.py); same EP rule
             from .moe import stack_experts, stack_route_weights, moe_rows
             local = [e for e in range(c.num_experts)
                      if self.tp_size <= 1 or e % self.tp_size == self.tp_rank]
             st = stack_experts(lw, local)
-            if not ops.moe_rows_supported(st["gw"], y.shape[1],
-                                          st["gw"].shape[1] // 2,
-                                          st["dw"].shape[1], st["group"],
-                                          st["packed"]):
+            if not (rows4 or ops.moe_rows_supported(
+                    st["gw"], y.shape[1], st["gw"].shape[1] // 2,
+                    st["dw"].shape[1], st["group"], st["packed"])):
                 st = None
         if st is not None:
             we = torch.zeros(T, c.num_experts, dtype=torch.float32,

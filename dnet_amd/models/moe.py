@@ -109,12 +109,39 @@ def int4_grouped(y: torch.Tensor, lw: LayerWeights) -> bool:
         return False
     if os.environ.get("DNET_MOE_INT4", "1") == "0":
         return False
-    for lin in (g0, d0):
-        if lin.bits != 4 or lin.mxfp4 or lin.group != g0.group:
-            return False
+    if not int4_bank(lw):
+        return False
     return ops.moe_int4_supported(y.shape[1], g0.w.shape[0] // 2,
                                   d0.w.shape[0], g0.group,
                                   g0.packed and d0.packed)
+
+
+def int4_bank(lw: LayerWeights) -> bool:
+    """Are both projections of the expert bank int4 with one group size
+    (a projection that Linear.make stored as int8 is not)?"""
+    g0 = lw.experts_gateup[0]
+    return all(lin.bits == 4 and not lin.mxfp4 and lin.group == g0.group
+               for lin in (g0, lw.experts_down[0]))
+
+
+def int4_rows(y: torch.Tensor, lw: LayerWeights, min_t: int) -> bool:
+    """Do y's rows take the token-routed MFMA path for int4 banks (moe_rows
+    over moe_rows_int4.hip.cpp)? GPU only, T >= min_t and T > 64, both
+    projections int4 and packed, dims ops.moe_rows_int4_supported accepts.
+    On by default (it measured faster than the loop from Mixtral's 8
+    experts up, docs/KERNELS.md "MoE rows int4"); DNET_MOE_INT4=0 or
+    DNET_MOE_ROWS_INT4=0 keeps the loop."""
+    T = y.shape[0]
+    if not y.is_cuda or T < min_t or T <= 64 or not int4_bank(lw):
+        return False
+    if os.environ.get("DNET_MOE_INT4", "1") == "0":
+        return False
+    if os.environ.get("DNET_MOE_ROWS_INT4", "1") == "0":
+        return False
+    g0, d0 = lw.experts_gateup[0], lw.experts_down[0]
+    return ops.moe_rows_int4_supported(y.shape[1], g0.w.shape[0] // 2,
+                                       d0.w.shape[0], g0.group,
+                                       g0.packed and d0.packed)
 
 
 class MoERingModel(RingModel):
@@ -245,8 +272,8 @@ class MoERingModel(RingModel):
     # experts' weights)
     DENSE_MOE_MAX_T = int(os.environ.get("DNET_DENSE_MOE_T", "64"))
     # from this many rows (and above DENSE_MOE_MAX_T), banks that
-    # ops.moe_rows_supported accepts take the token-routed MFMA path
-    # instead of the per-expert loop
+    # ops.moe_rows_supported accepts, and int4 banks under int4_rows, take
+    # the token-routed MFMA path instead of the per-expert loop
     ROWS_MOE_MIN_T = int(os.environ.get("DNET_MOE_ROWS_T", "65"))
     GLU = 0                 # 0 = SwiGLU, 1 = gpt-oss clamped GLU
     GLU_ALPHA = 1.702
@@ -304,14 +331,16 @@ class MoERingModel(RingModel):
             if getattr(lw, "shared_gateup", None) is not None:
                 out = out + self._shared_expert(y, lw)
             return out.to(y.dtype)
-        if (y.is_cuda and T >= self.ROWS_MOE_MIN_T
-                and T > self.DENSE_MOE_MAX_T
-                and (eg0.bits in (8, 16) or eg0.mxfp4)):
+        rows4 = (T > self.DENSE_MOE_MAX_T
+                 and int4_rows(y, lw, self.ROWS_MOE_MIN_T))
+        if rows4 or (y.is_cuda and T >= self.ROWS_MOE_MIN_T
+                     and T > self.DENSE_MOE_MAX_T
+                     and (eg0.bits in (8, 16) or eg0.mxfp4)):
             st = self._expert_stack(lw)
-            if ops.moe_rows_supported(st["gw"], y.shape[1],
-                                      st["gw"].shape[1] // 2,
-                                      st["dw"].shape[1], st["group"],
-                                      st["packed"]):
+            if rows4 or ops.moe_rows_supported(st["gw"], y.shape[1],
+                                               st["gw"].shape[1] // 2,
+                                               st["dw"].shape[1],
+                                               st["group"], st["packed"]):
                 we = torch.zeros(T, c.num_experts, dtype=torch.float32,
                                  device=y.device)
                 we.scatter_(1, idx, weights)

@@ -610,12 +610,31 @@ def moe_rows_supported(w: torch.Tensor, K: int, I: int, H: int, group: int,
     The kernels also run bf16 banks and int8 banks in the pack_int8_mfma
     layout (group % 64 == 0), and the ops accept them, but at 8192 rows
     they measured 2-3x slower than the per-expert loop (docs/KERNELS.md,
-    "MoE rows"), so those formats stay on the loop, as do unpacked int8
-    and grouped int4 (also uint8, group 128), which the kernels do not
-    serve at all."""
+    "MoE rows"), so those formats stay on the loop, as does unpacked int8,
+    which the kernels do not serve at all. Grouped int4 (also uint8, bf16
+    scales, group % 128 == 0) is not this predicate's business: it has
+    kernels of its own behind the same ops, see moe_rows_int4_supported."""
     if K % 64 or I % 64 or H % 64:
         return False
     return bool(w.dtype == torch.uint8 and group == 32 and not packed)
+
+
+def moe_rows_int4_supported(K: int, I: int, H: int, group: int,
+                            packed: bool) -> bool:
+    """Do moe_gateup_rows / moe_down_rows serve an int4 expert bank (gate/up
+    [E,2I,K/2], down [E,H,I/2], bf16 group scales) on the GPU? The kernels
+    of moe_rows_int4.hip.cpp take the pack_int4_mfma layout with K, I and
+    the group multiples of 128, the group dividing K and I, and H a
+    multiple of 64. Whether the models use them by default is their
+    decision (models/moe.py, int4_rows)."""
+    if not packed or group <= 0 or group % 128:
+        return False
+    return not (K % 128 or I % 128 or K % group or I % group or H % 64)
+
+
+def _is_int4_bank(w: torch.Tensor, scales) -> bool:
+    return (w.dtype == torch.uint8 and scales is not None
+            and scales.dtype == torch.bfloat16)
 
 
 def moe_route(we: torch.Tensor, topk: int) -> dict:
@@ -664,10 +683,19 @@ def moe_gateup_rows(x: torch.Tensor, gw: torch.Tensor, gs, gb, plan: dict,
     -> act [slots_cap, I] bf16, compact in the plan's slot order:
     act[slot] = glu(x[t] . Wg[e]^T + bg, x[t] . Wu[e]^T + bu). Rows past
     the live slots are never written (nor read by moe_down_rows). A slot's
-    bits depend on its own token only."""
+    bits depend on its own token only. A uint8 bank with bf16 scales is
+    int4 (uint8 scales: mxfp4) and runs the 128-row kernels of
+    moe_rows_int4.hip.cpp, which need ``packed`` and the dims of
+    moe_rows_int4_supported."""
     if x.is_cuda:
         act = torch.empty(plan["slots_cap"], gw.shape[1] // 2,
                           dtype=torch.bfloat16, device=x.device)
+        if _is_int4_bank(gw, gs):
+            _native().moe_rows_int4_gateup(
+                x, gw, gs, gb, plan["slot_token"], plan["offsets"],
+                plan["tiles"], plan["ntiles"], act, group, packed, glu,
+                alpha, limit)
+            return act
         _native().moe_rows_gateup(x, gw, gs, gb, plan["slot_token"],
                                   plan["tiles"], plan["ntiles"], act, group,
                                   packed, glu, alpha, limit)
@@ -683,13 +711,21 @@ def moe_down_rows(act: torch.Tensor, dw: torch.Tensor, ds, db,
     [E,H,I], we [T,E] (the weights the plan was made from) -> out [T,H]
     f32, out[t] = sum_e we[t,e] * (act[slot(t,e)] . Wd[e]^T + bd[e]) over
     the token's slots in ascending-e order; exact zeros for a token with
-    no routed expert. Fixed summation order, no atomics."""
+    no routed expert. Fixed summation order, no atomics. int4 banks
+    (uint8 with bf16 scales) take the kernels of moe_rows_int4.hip.cpp,
+    as in moe_gateup_rows."""
     if act.is_cuda:
         H = dw.shape[1]
         y = torch.empty(plan["slots_cap"], H, dtype=torch.float32,
                         device=act.device)
         out = torch.empty(plan["T"], H, dtype=torch.float32,
                           device=act.device)
+        if _is_int4_bank(dw, ds):
+            _native().moe_rows_int4_down(
+                act, dw, ds, db, we.contiguous(), plan["slot_token"],
+                plan["token_slots"], plan["offsets"], plan["tiles"],
+                plan["ntiles"], y, out, group, packed)
+            return out
         _native().moe_rows_down(act, dw, ds, db, we.contiguous(),
                                 plan["slot_token"], plan["token_slots"],
                                 plan["tiles"], plan["ntiles"], y, out, group,

@@ -26,7 +26,8 @@ def _sources() -> list[Path]:
 # (v_pk_{add,mul,fma}_f32) switched off.
 _NO_PACKED_F32 = {"attn_prefill_kv.hip.cpp", "rope_append_rows.hip.cpp",
                   "mla_decode.hip.cpp", "moe_rows.hip.cpp",
-                  "mla_prefill.hip.cpp", "moe_int4.hip.cpp"}
+                  "mla_prefill.hip.cpp", "moe_int4.hip.cpp",
+                  "moe_rows_int4.hip.cpp"}
 _NO_PACKED_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang",
                         "-packed-fp32-ops"]
 

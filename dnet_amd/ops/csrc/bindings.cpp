@@ -100,6 +100,20 @@ void moe_rows_down(torch::Tensor act, torch::Tensor w,
                    torch::Tensor slot_token, torch::Tensor token_slots,
                    torch::Tensor tiles, torch::Tensor ntiles, torch::Tensor y,
                    torch::Tensor out, int64_t group, bool packed);
+void moe_rows_int4_gateup(torch::Tensor x, torch::Tensor w,
+                          c10::optional<torch::Tensor> scales,
+                          c10::optional<torch::Tensor> bias,
+                          torch::Tensor slot_token, torch::Tensor offsets,
+                          torch::Tensor tiles, torch::Tensor ntiles,
+                          torch::Tensor act, int64_t group, bool packed,
+                          int64_t glu, double alpha, double limit);
+void moe_rows_int4_down(torch::Tensor act, torch::Tensor w,
+                        c10::optional<torch::Tensor> scales,
+                        c10::optional<torch::Tensor> bias, torch::Tensor we,
+                        torch::Tensor slot_token, torch::Tensor token_slots,
+                        torch::Tensor offsets, torch::Tensor tiles,
+                        torch::Tensor ntiles, torch::Tensor y,
+                        torch::Tensor out, int64_t group, bool packed);
 void col_norm2(torch::Tensor x, torch::Tensor norms);
 void gather_cols(torch::Tensor x, torch::Tensor idx, torch::Tensor out);
 void scatter_cols(torch::Tensor in, torch::Tensor idx, torch::Tensor out);
@@ -209,6 +223,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "token-routed MFMA gate/up GEMM with fused GLU over the tile list");
   m.def("moe_rows_down", &dnet::moe_rows_down,
         "token-routed MFMA down GEMM + fixed-order per-token combine");
+  m.def("moe_rows_int4_gateup", &dnet::moe_rows_int4_gateup,
+        "token-routed MFMA gate/up GEMM for int4 banks, 128-row tile pairs");
+  m.def("moe_rows_int4_down", &dnet::moe_rows_int4_down,
+        "token-routed MFMA down GEMM for int4 banks + per-token combine");
   m.def("col_norm2", &dnet::col_norm2, "per-column L2 norms");
   m.def("gather_cols", &dnet::gather_cols, "pack kept columns");
   m.def("scatter_cols", &dnet::scatter_cols, "zero + scatter kept columns");

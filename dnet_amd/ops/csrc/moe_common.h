@@ -1,6 +1,6 @@
 // Helpers shared by the grouped MoE kernels (moe.hip.cpp: M <= 64 rows,
 // moe_int4.hip.cpp: its MFMA pair for int4 banks, moe_rows.hip.cpp:
-// token-routed MFMA path).
+// token-routed MFMA path, moe_rows_int4.hip.cpp: that path for int4 banks).
 #pragma once
 
 #include "common.h"
@@ -33,6 +33,11 @@ void moe_int4_down(torch::Tensor act, torch::Tensor w,
                    torch::Tensor out, int64_t group);
 
 void moe_int4_force_ks(int64_t ks);
+
+// out[t, :] = sum of y over token_slots[t] in order (moe_rows.hip.cpp);
+// the launch that ends moe_rows_down and moe_rows_int4_down.
+void moe_rows_combine(const torch::Tensor& y, const torch::Tensor& token_slots,
+                      torch::Tensor& out, hipStream_t stream);
 
 // uint8 banks come in two formats, told apart by the scales: bf16 group
 // scales = int4, e8m0 uint8 block scales = mxfp4.

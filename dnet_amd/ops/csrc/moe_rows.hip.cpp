@@ -420,6 +420,16 @@ __global__ __launch_bounds__(256) void moe_rows_combine_kernel(
   }
 }
 
+// the combine launch, shared with moe_rows_int4.hip.cpp (checked tensors)
+void moe_rows_combine(const torch::Tensor& y, const torch::Tensor& token_slots,
+                      torch::Tensor& out, hipStream_t stream) {
+  hipLaunchKernelGGL(moe_rows_combine_kernel, dim3((unsigned)out.size(0)),
+                     dim3(256), 0, stream, (const float*)y.data_ptr(),
+                     (const int*)token_slots.data_ptr(),
+                     (float*)out.data_ptr(), (int)out.size(1),
+                     (int)token_slots.size(1));
+}
+
 static bool is_i32(const torch::Tensor& t) {
   return t.scalar_type() == torch::kInt && t.is_contiguous();
 }
@@ -561,11 +571,7 @@ void moe_rows_down(torch::Tensor act, torch::Tensor w,
       (const int*)ntiles.data_ptr(), (const float*)we.data_ptr(), nullptr,
       (float*)y.data_ptr(), (int)I, (int)H, (int)E,
       (int)std::max<int64_t>(group, 64), 0.f, 0.f);
-  hipLaunchKernelGGL(moe_rows_combine_kernel, dim3((unsigned)T), dim3(256), 0,
-                     stream, (const float*)y.data_ptr(),
-                     (const int*)token_slots.data_ptr(),
-                     (float*)out.data_ptr(), (int)H,
-                     (int)token_slots.size(1));
+  moe_rows_combine(y, token_slots, out, stream);
 }
 
 }  // namespace dnet
