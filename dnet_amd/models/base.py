@@ -29,13 +29,25 @@ from .config import ModelConfig, QuantConfig
 # raises TTFT ~45% vs dequant+matmul).
 GEMV_MAX_M = 64
 
+# Quantized linears with GEMV_MAX_M < M <= GEMM_ROWS_MAX_M rows multiply
+# from the packed bytes in ops.gemm_rows (fused dequant, no bf16 copy of
+# the weights); above the cap the dequant+hipBLASLt path runs. 64 turns the
+# route off, and that is the default: measured, no M makes the fused kernel
+# faster on every layer shape (profiles/r12_gemm_rows.md).
+# DNET_GEMM_ROWS_T overrides it.
+GEMM_ROWS_MAX_M = int(os.environ.get("DNET_GEMM_ROWS_T", "64"))
+
 
 class Linear:
     """A weight-only-quantizable linear: y = x @ W^T + b.
 
-    Small-M (decode) goes through the fused HIP GEMV; large-M (prefill)
-    through hipBLASLt via torch.matmul (dequantizing int8 tiles to a scratch
-    buffer first).
+    Small-M (decode, M <= GEMV_MAX_M) goes through the fused HIP GEMV /
+    MFMA decode GEMM. Packed int8 / int4 weights with up to
+    GEMM_ROWS_MAX_M rows go through ops.gemm_rows, the fused-dequant MFMA
+    prefill GEMM that multiplies from the quantized bytes. Everything else
+    (more rows, bf16, MXFP4, unpacked or unaligned weights) goes through
+    hipBLASLt via torch.matmul, dequantizing the weights to a transient
+    bf16 tensor first.
     """
 
     def __init__(self, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -140,12 +152,28 @@ class Linear:
                 return ops.gemv_int8(x, self.w, self.scales, self.group,
                                      self.bias, self.packed)
             return ops.gemv_bf16(x, self.w, self.bias)
+        # any other x (not 2-D bf16) keeps the matmul path it always had
+        if (x.dim() == 2 and x.dtype == torch.bfloat16
+                and self.rows_fused(m)):
+            self._wd = None
+            return ops.gemm_rows(x, self.w, self.scales, self.group,
+                                 self.bias, self.bits)
         wd, self._wd = (self._wd, None) if self._wd is not None \
             else (self.dequant(), None)
         y = x @ wd.t()
         if self.bias is not None:
             y = y + self.bias
         return y
+
+    def rows_fused(self, m: int) -> bool:
+        """Does a call with m rows take ops.gemm_rows (and so need no
+        dequantized copy of the weights)?"""
+        return (GEMV_MAX_M < m <= GEMM_ROWS_MAX_M and self.is_quant
+                and not self.mxfp4 and self.w.is_cuda
+                and ops.gemm_rows_supported(m, self.out_features,
+                                            self.scales.shape[1] * self.group,
+                                            self.group, self.bits,
+                                            self.packed))
 
     def nbytes(self) -> int:
         n = self.w.numel() * self.w.element_size()
@@ -820,10 +848,13 @@ class RingModel:
             return ops.DEFERRED
         return dl(a)
 
-    def _dequant_prefetch(self, layer_ids: Sequence[int], i: int):
+    def _dequant_prefetch(self, layer_ids: Sequence[int], i: int,
+                          rows: int = 0):
         """Side-stream dequant of layer i+1's dense weights while layer i
         computes (prefill only; ~65 ms of the 64x128 TTFT was serial
-        dequant). Returns an event the consumer waits on, or None."""
+        dequant). ``rows`` is the row count (B * T) of the prefill: linears
+        that will multiply from the packed bytes (Linear.rows_fused) are
+        skipped. Returns an event the consumer waits on, or None."""
         if (self.device.type != "cuda" or i + 1 >= len(layer_ids)
                 or self.weight_provider is not None):  # offload streams
             return None
@@ -840,7 +871,8 @@ class RingModel:
         consumer = torch.cuda.current_stream()
         with torch.cuda.stream(self._dq_stream):
             for lin in (nxt.qkv, nxt.o, nxt.gateup, nxt.down):
-                if lin is not None and lin.is_quant:
+                if (lin is not None and lin.is_quant
+                        and not lin.rows_fused(rows)):
                     wd = lin.dequant()
                     wd.record_stream(consumer)
                     lin._wd = wd
@@ -860,7 +892,7 @@ class RingModel:
         nq, nkv, d = self.nq_local, self.nkv_local, c.head_dim
         positions = torch.arange(p0, p0 + T, device=h.device)
         layer_ids = list(layer_ids)
-        dq_ev = self._dequant_prefetch(layer_ids, -1)  # prefetch layer 0
+        dq_ev = self._dequant_prefetch(layer_ids, -1, B * T)  # layer 0
         # in-place path: fused RoPE+append of the chunk's rows, then flash
         # attention straight off the (bf16 or int8) cache. No torch rope,
         # no slot dequant, no K/V/q/out copies. DNET_PREFILL_INPLACE=0
@@ -873,7 +905,7 @@ class RingModel:
             lw = self._layer(lid)
             if dq_ev is not None:
                 torch.cuda.current_stream().wait_event(dq_ev)
-            dq_ev = self._dequant_prefetch(layer_ids, i)
+            dq_ev = self._dequant_prefetch(layer_ids, i, B * T)
             flat = h.view(B * T, H)
             y = ops.rmsnorm(flat, None, lw.attn_norm, c.rms_eps)
             qkv = lw.qkv(y)

@@ -151,6 +151,59 @@ def gemv_int4(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
     return ref.gemv_int4(x, w, scales, group, bias)
 
 
+def gemm_rows_supported(M: int, N: int, K: int, group: int, bits: int,
+                        packed: bool) -> bool:
+    """Can gemm_rows (the fused-dequant MFMA prefill GEMM, M > 64) take
+    this call? Needs the native library, the packed MFMA weight layout,
+    int8 with K % 64 == 0 and group % 64 == 0 or int4 with K % 128 == 0
+    and group % 128 == 0 (group dividing K), and more than 64 rows: up to
+    64 the decode GEMM is the kernel."""
+    if not (packed and bits in (8, 4) and has_native()):
+        return False
+    align = 64 if bits == 8 else 128
+    return (M > 64 and N > 0 and K > 0 and group > 0 and K % align == 0
+            and group % align == 0 and K % group == 0)
+
+
+def gemm_rows(x: torch.Tensor, w: torch.Tensor, scales: torch.Tensor,
+              group: int, bias: torch.Tensor | None = None,
+              bits: int = 8) -> torch.Tensor:
+    """out[M, N] = x[M, K] @ W[N, K]^T (+ bias) for bf16 CUDA x with more
+    than 64 rows, W int8 (pack_int8_mfma) or int4 (pack_int4_mfma) with
+    bf16 group scales [N, K/group]. Multiplies from the packed bytes
+    (weights enter as bf16(q*s), f32 accumulation, one bf16 rounding, K
+    never split): a row's bits depend on that row alone."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2):
+        raise ValueError("gemm_rows: x must be a 2-D bf16 CUDA tensor")
+    if bits not in (8, 4):
+        raise ValueError(f"gemm_rows: bits must be 8 or 4, got {bits}")
+    M, K = x.shape
+    if not (w.dim() == 2 and scales.dim() == 2 and w.device == x.device
+            and scales.device == x.device):
+        raise ValueError("gemm_rows: w and scales are 2-D, on x's device")
+    N = w.shape[0]
+    if w.dtype != (torch.int8 if bits == 8 else torch.uint8) \
+            or w.shape[1] != (K if bits == 8 else K // 2):
+        raise ValueError("gemm_rows: w must be packed int8 [N, K] "
+                         "(bits=8) or packed uint8 [N, K/2] (bits=4)")
+    if not gemm_rows_supported(M, N, K, group, bits, True):
+        _native()     # a missing library is reported as such
+        raise ValueError(
+            f"gemm_rows: unsupported call M={M} N={N} K={K} group={group} "
+            f"bits={bits} (M > 64; int8 K, group % 64; int4 K, group % 128)")
+    if scales.dtype != torch.bfloat16 or tuple(scales.shape) != (N, K // group):
+        raise ValueError("gemm_rows: scales must be bf16 [N, K/group]")
+    if bias is not None and not (bias.dtype == torch.bfloat16
+                                 and bias.numel() == N
+                                 and bias.device == x.device):
+        raise ValueError("gemm_rows: bias must be bf16 [N] on x's device")
+    out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _native().gemm_rows(x.contiguous(), w.contiguous(), scales.contiguous(),
+                        None if bias is None else bias.contiguous(), out,
+                        group, bits)
+    return out
+
+
 def dequant_int4(w: torch.Tensor, scales: torch.Tensor, group: int,
                  packed: bool = True) -> torch.Tensor:
     if w.is_cuda:

@@ -74,6 +74,9 @@ int64_t gemm_m16(torch::Tensor x, torch::Tensor w,
                  c10::optional<torch::Tensor> bias, torch::Tensor out,
                  c10::optional<torch::Tensor> partials, int64_t group,
                  bool packed, int64_t bits, bool defer_combine);
+void gemm_rows(torch::Tensor x, torch::Tensor w, torch::Tensor scales,
+               c10::optional<torch::Tensor> bias, torch::Tensor out,
+               int64_t group, int64_t bits);
 void moe_gateup(torch::Tensor x, torch::Tensor w,
                 c10::optional<torch::Tensor> scales,
                 c10::optional<torch::Tensor> bias, torch::Tensor we,
@@ -211,6 +214,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("partials"), py::arg("group"),
         py::arg("packed"), py::arg("bits"),
         py::arg("defer_combine") = false);
+  m.def("gemm_rows", &dnet::gemm_rows,
+        "fused-dequant MFMA prefill GEMM for packed int8/int4 (M > 64)",
+        py::arg("x"), py::arg("w"), py::arg("scales"), py::arg("bias"),
+        py::arg("out"), py::arg("group"), py::arg("bits"));
   m.def("moe_gateup", &dnet::moe_gateup,
         "grouped MoE gate+up GEMV with fused GLU and expert skip");
   m.def("moe_down", &dnet::moe_down,
